@@ -6,25 +6,31 @@ lengthscale, W, kappa, Z), inputs resident in HBM, parameters re-uploaded and gr
 Workload (config.workload): the headline config H of BASELINE.md -- T=4 [Gaussian, Bernoulli, Poisson, Gamma]
 (Df=5), N_t=200 000 rows per task, M=1024 inducing points, Q=3 latent GPs, P=1, synthetic data.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 N>1 is launched by torch.distributed.run (one rank per GPU, RCCL): the rows of every task are sharded over the ranks
 (strong scaling: total work fixed), each rank uploads and streams only its rows (`hmogp_step_begin`), the statistic
 bundle is sum-all-reduced once per step in its wire format (lower triangles of H_q, 12.7 MB), `hmogp_step_finish` runs
 replicated.  `python bench.py --gpus N` without a rendezvous in the environment launches itself under
 torch.distributed.run.
 
+A plain run sets up, warms up, times exactly K steps and prints the line; everything measured beside the headline
+(the entries marked [full] below) runs only with --full.  --dump-outputs DIR writes what the last timed step returned
+(ELBO, KL terms, every gradient, condition estimates, jitter rungs) as DIR/<name>.npy in float64 (a fixed, seeded
+sample of any array beyond the 64 MB budget); the inputs are seeded, so two builds can be compared output for output.
+
 Rank 0 prints ONE JSON line with the contract fields plus
   roofline      FP64-MFMA roofline of the dominant kernel (forward N x M x M contraction P~ = K^ C_q)
-  roofline_kuf  HBM roofline of K_uf construction (rbf_cross_cov), the kernel the north-star singles out
-  cpu_baseline  baseline B: the NumPy/BLAS oracle ("port", all host cores) timed at two row samples (N=1 only), next
+  roofline_kuf  [full] HBM roofline of K_uf construction (rbf_cross_cov), the kernel the north-star singles out
+  cpu_baseline  [full] baseline B: the NumPy/BLAS oracle ("port", all host cores) timed at two row samples (N=1 only), next
                 to the host's plain dgemm rate (host_dgemm_gflops) so that the port's efficiency is visible
-  cpu_baseline_literal  baseline A: the literal reference algorithm (N x N terms) at C1 and up to N_t = 8192
-  parity_at_headline_M  engine vs oracle on the sampled rows at the headline M (the bench fails above 1e-5)
-  other_configs the other BASELINE.json configurations (C1, C2, C3 as the facade's SVI loop over N_all = 1M, the per-rank
+  cpu_baseline_literal  [full] baseline A: the literal reference algorithm (N x N terms) at C1 and up to N_t = 8192
+  parity_at_headline_M  [full] engine vs oracle on the sampled rows at the headline M (the bench fails above 1e-5)
+  other_configs [full] the other BASELINE.json configurations (C1, C2, C3 as the facade's SVI loop over N_all = 1M, the per-rank
                 share of C4, C5 + predict_f on a 256 x 256 grid), a few steps each, with executed flops and the fraction
                 of the FP64-MFMA peak (N=1 only; these are reported beside `value`, never mixed into it)
   N > 1: exchange_modes_ms_per_step times the step with the library's own RCCL communicator ("native", the default) and
-         with the torch.distributed all-reduce on the aliased wire buffer ("device"); replicated_ms_per_rank.
+         [full] with the torch.distributed all-reduce on the aliased wire buffer ("device"); replicated_ms_per_rank.
+  exact_zero_windows  [full] the same workload in the opt-in exact-zero-window mode (N=1 only)
 """
 import argparse
 import json
@@ -93,9 +99,13 @@ def main():
     ap.add_argument("--no-wakeup", action="store_true", help="skip the ~0.3 s synthetic device wake-up before the warm-up steps")
     ap.add_argument("--force-dist", action="store_true",
                     help="--gpus 1 only: run the DISTRIBUTED code path (nccl process group, StatsReducer negotiation, native RCCL "
-                         "communicator, hmogp_elbo_grad_sharded, the alternative-exchange-mode loop, teardown order) with a world "
+                         "communicator, hmogp_elbo_grad_sharded, the alternative-exchange-mode loop with --full, teardown order) with a world "
                          "of ONE rank -- a dry run of everything a multi-GPU launch executes, on a 1-GPU box")
     ap.add_argument("--no-exact-zero-pass", action="store_true", help="skip the extra (untimed-for-value) opt-in mode pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the headline: K_uf roofline alone, exact-zero pass, other "
+                         "configurations, CPU baselines and parity, the alternative exchange modes (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -187,12 +197,15 @@ def main():
         rows_all = [int(r[2]) for r in fwd_rank]
     if not np.isfinite(out["elbo"]):
         raise SystemExit("bench.py: non-finite ELBO")
+    if args.dump_outputs and rank == 0:     # (before any other pass: the engine overwrites its output arrays in place)
+        dump_outputs(args.dump_outputs, out)
 
-    # ---- N > 1: the same steps with the other exchange modes (reported, not `value`) ------------------------------------
+    # ---- N > 1: the same steps with the other exchange modes (reported, not `value`; the default mode's entry only without --full)
     exchange_modes, repl_all = {}, None
     if distm:
         exchange_modes = hdist.exchange_mode_sweep(
             eng, step, reducer, args.steps, args.warmup, fence, local_rank, elapsed, cat_ms,
+            alternatives=("native", "device") if args.full else (),
             make_reducer=lambda alt: hdist.StatsReducer(eng, device=local_rank, mode=alt, single_rank_exchange=args.force_dist))
         repl_all = [r[0] for r in hdist.gather_floats([cat_ms["mxm_algebra"] / args.steps], world, local_rank)]
 
@@ -239,7 +252,8 @@ def main():
             # launches of 16384 rows interleaved with the latency-bound K_uu chain, so its in-step SPAN (in_step_*) includes
             # that chain; the roofline is quoted on the same kernel launched alone, one (task, all latents) launch shape
             # (kuf_alone(), HIP events around `iters` back-to-back launches).
-            "roofline_kuf": kuf_alone(N, M, Q, kuf_gbs, cat_ms["rbf_cross_cov"] / args.steps, cat_n["rbf_cross_cov"] // args.steps),
+            **({"roofline_kuf": kuf_alone(N, M, Q, kuf_gbs, cat_ms["rbf_cross_cov"] / args.steps,
+                                          cat_n["rbf_cross_cov"] // args.steps)} if args.full else {}),
             # the whole step against the FP64-MFMA peak on EXECUTED contraction flops (3 n M^2 per (row, latent) pair: the
             # Gram only forms lower tiles), this rank's share
             "step_tflops_executed": exec_flops / (elapsed / args.steps) / 1e12,
@@ -274,13 +288,13 @@ def main():
             line["replicated_ms_per_rank"] = repl_all
         if args.force_dist:
             line["force_dist"] = True       # one-rank dry run of the distributed path: no other configurations, no CPU legs
-        if world == 1 and not distm and not args.no_exact_zero_pass:
+        if args.full and world == 1 and not distm and not args.no_exact_zero_pass:
             line["exact_zero_windows"] = exact_zero_pass(args, prm, X, Y, N, M, Q, P, out)
         # GPU legs first, CPU legs last: after the full-size CPU baseline (64 worker threads x BLAS threads, ~20 s of all host
         # cores) the launch-latency-bound chains of the small configurations measured 0.3 ms slower (host-side launch jitter)
-        if world == 1 and not distm and not args.no_other_configs:
+        if args.full and world == 1 and not distm and not args.no_other_configs:
             line["other_configs"] = other_configs(args)   # (the headline engine keeps its 40 GB of row workspaces: 288 GB of HBM)
-        if world == 1 and not distm and not args.no_cpu_baseline:
+        if args.full and world == 1 and not distm and not args.no_cpu_baseline:
             line.update(cpu_baselines(args, eng, prm, X, Y, N, M, Q, P))
             eng.close()
         if "other_configs" in line:     # compact recap as the LAST key: a tail of the line still shows every configuration
@@ -291,6 +305,27 @@ def main():
         sys.stdout.flush()
     if distm:
         hdist.teardown(reducer)             # ncclCommDestroy of the library's own communicator, on every rank, before torch's
+
+
+DUMP_KEYS = ("elbo", "kl", "g_m_u", "g_L_u", "g_variance", "g_lengthscale", "g_W", "g_kappa", "g_Z", "cond_est", "rung")
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, out):
+    """What a caller of the timed path receives from its last step, one float64 .npy per array.  Beyond DUMP_BUDGET_BYTES in all,
+    every array larger than an equal share of the budget is replaced by a fixed sample of its flattened entries (RandomState(0),
+    sorted indices: the same entries for the same shape in every run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {k: np.array(out[k], dtype=np.float64) for k in DUMP_KEYS if out.get(k) is not None}
+    if sum(a.nbytes for a in arrs.values()) > DUMP_BUDGET_BYTES:
+        share = DUMP_BUDGET_BYTES // (8 * len(arrs))
+        for k, a in arrs.items():
+            if a.size > share:
+                idx = np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))
+                arrs[k] = a.ravel()[idx]
+    for k, a in arrs.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def kuf_alone(N, M, Q, in_step_gbs, in_step_ms, in_step_launches):

@@ -296,7 +296,7 @@ def test_bench_self_launches_two_ranks():
         pytest.skip("needs >= 2 GPUs")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows",
-                        "20000", "--inducing", "256"], env=env, capture_output=True, text=True, timeout=800)
+                        "20000", "--inducing", "256", "--full"], env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and sum(line["rows_per_rank"]) == 4 * 20000
@@ -324,7 +324,7 @@ def test_bench_force_dist_one_rank_dry_run():
         assert len(lines) == 1, r.stdout[-2000:]                      # the contract: ONE JSON line on stdout
         return json.loads(lines[0])
 
-    forced = run(["--force-dist"])
+    forced = run(["--force-dist", "--full"])          # (--full: the alternative-exchange-mode loop too)
     plain = run(["--no-other-configs", "--no-cpu-baseline", "--no-exact-zero-pass"])
     assert forced["force_dist"] is True and forced["n_gpus"] == 1 and forced["rccl_ranks"] == 1
     assert forced["reducer_mode"] == "native" and forced["allreduce_ms_per_step"] > 0.0
@@ -342,6 +342,37 @@ def test_bench_force_dist_one_rank_dry_run():
     assert forced["ms_per_step"] < 1.25 * plain["ms_per_step"] + 0.5               # ... in the same time (+ one-rank exchange)
     print("force-dist %.3f ms/step (exchange %.3f) vs plain %.3f ms/step; modes %s" % (
         forced["ms_per_step"], forced["allreduce_ms_per_step"], plain["ms_per_step"], forced["exchange_modes_ms_per_step"]))
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """`python bench.py --gpus 1 --dump-outputs DIR` without --full: one JSON line with the headline fields only, and the outputs of
+    the last timed step in DIR as float64 .npy files, identical from run to run (seeded inputs, deterministic kernels)."""
+    import json
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows",
+                            "20000", "--inducing", "256", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=500)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    line = run(tmp_path / "a")
+    assert line["steps"] == 3 and line["ms_per_step"] > 0.0 and line["unit"] == "steps/s" and line["dtype"] == "f64"
+    assert abs(line["value"] - 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]
+    assert not set(line) & {"roofline_kuf", "exact_zero_windows", "other_configs", "cpu_baseline", "parity_at_headline_M"}
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert {"elbo.npy", "g_m_u.npy", "g_L_u.npy", "g_Z.npy", "g_W.npy"} <= set(names)
+    a = {n: np.load(str(tmp_path / "a" / n)) for n in names}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert float(a["elbo.npy"]) == line["elbo"] and a["g_L_u.npy"].shape == (256 * 257 // 2, 3)
+    run(tmp_path / "b")
+    for n in names:
+        assert np.array_equal(a[n], np.load(str(tmp_path / "b" / n))), n
 
 
 def _facade_nccl_worker(rank, world, port, q):

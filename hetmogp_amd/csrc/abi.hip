@@ -427,6 +427,7 @@ int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t 
     need_device(device);
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);
+    check_lik_param(lik_id, lik_param);
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !y || !m || !v || !ve || !dm || !dv)
       throw EngineError{HMOGP_E_INVALID, "bad arguments"};
     DevBuf dy, dmm, dvv, dve, ddm, ddv;
@@ -449,6 +450,7 @@ int hmogp_predictive(int32_t device, int32_t lik_id, double lik_param, int32_t g
     need_device(device);
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);
+    check_lik_param(lik_id, lik_param);
     const int Jp = (lik_id == HMOGP_LIK_CATEGORICAL) ? J : 1;  // dim_p of the reference's get_metadata()
     if (gh_T == 0) gh_T = (lik_id == HMOGP_LIK_CATEGORICAL) ? 10 : 20;
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !m || !v || !mean || !var || (gh_T != 10 && gh_T != 20))
@@ -470,6 +472,7 @@ int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64
   return guarded(nullptr, [&] {
     need_device(device);
     const int J = lik_dimf(lik_id, lik_param);
+    check_lik_param(lik_id, lik_param);
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || num_samples < 1 || !y || !m || !v || !log_pred)
       throw EngineError{HMOGP_E_INVALID, "bad arguments"};
     if (lik_id == HMOGP_LIK_GAMMA || lik_id == HMOGP_LIK_BETA)
@@ -491,6 +494,7 @@ int hmogp_sample(int32_t device, int32_t lik_id, double lik_param, int64_t N, ui
     need_device(device);
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);
+    check_lik_param(lik_id, lik_param);
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !F || !Y) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
     DevBuf dF, dY;
     dF.ensure(sizeof(double) * N * J), dY.ensure(sizeof(double) * N);

@@ -136,6 +136,7 @@ void hmogp_engine::init(const hmogp_config* c) {
     k.param = c->lik_param ? c->lik_param[t] : 0.0;
     if (k.lik == HMOGP_LIK_GAUSSIAN && !(k.param > 0.0)) k.param = 0.5;  // gaussian.py:21-24
     k.dimf = lik_dimf(k.lik, k.param);
+    check_lik_param(k.lik, k.param);
     if (k.dimf < 1 || k.dimf > HMOGP_MAXJ) throw EngineError{HMOGP_E_INVALID, "unsupported likelihood / dim_f"};
     k.d0 = d;
     for (int j = 0; j < k.dimf; ++j, ++d)

@@ -107,6 +107,7 @@ struct Task {
 };
 
 int lik_dimf(int lik, double param);
+void check_lik_param(int lik, double param);  // HMOGP_E_INVALID for a parameter the likelihood has no value for (Student: nu)
 
 // Row ranges per weighted-Gram launch: a multiple of 8 (one range per XCD at a time), each >= 32 k-steps of 16 rows,
 // enough blocks (lower tiles x ranges) for >= 8 rounds over the 256 CUs, at most KS_MAX slabs.

@@ -13,10 +13,16 @@ int lik_dimf(int lik, double param) {
     case HMOGP_LIK_EXPONENTIAL: return 1;
     case HMOGP_LIK_HETGAUSSIAN:
     case HMOGP_LIK_GAMMA:
-    case HMOGP_LIK_BETA: return 2;
+    case HMOGP_LIK_BETA:
+    case HMOGP_LIK_STUDENT: return 2;
     case HMOGP_LIK_CATEGORICAL: return (int)param - 1;
     default: return -1;
   }
+}
+
+void check_lik_param(int lik, double param) {
+  if (lik == HMOGP_LIK_STUDENT && !(std::isfinite(param) && param > 0.0))
+    throw EngineError{HMOGP_E_INVALID, "Student: deg_free must be finite and > 0"};
 }
 
 int gram_ksplit(long long n, int M) {

@@ -1,11 +1,12 @@
 // lik_device.h -- device-side variational expectations E_q(f)[log p(y|f)] and their derivatives with respect to
 // the mean / variance of q(f), for the eight likelihoods of /root/reference/likelihoods/*.py (SURVEY.md 8a, rows
-// L1-L8).  Results reproduce the reference's formulas including its clips and quirks:
+// L1-L8) and the heteroscedastic Student-t the reference only stubs (student.py; contract: DESIGN 9).  Results
+// reproduce the reference's formulas including its clips and quirks:
 //   Q1  Gamma / Beta: Gauss-Hermite weights divided by sqrt(pi) twice (gamma.py:110,139-141; beta.py:113,142-144)
 //   Q2  Categorical: d/dm is the constant onehot(y)[d] - 1 (categorical.py:102-113)
 // Lane mapping: closed forms, 1-D quadratures and Gamma (separable in its two functions) use ONE lane per row;
-// Beta (100 nodes) and Categorical (10^(K-1) nodes) use ONE WAVE per row, nodes strided over the 64 lanes and
-// reduced with wavefront shuffles.
+// Beta (100 nodes), Student (400 nodes) and Categorical (10^(K-1) nodes) use ONE WAVE per row, nodes strided over the
+// 64 lanes and reduced with wavefront shuffles.
 #pragma once
 #include "common.h"
 #include "gh_tables.h"
@@ -146,7 +147,8 @@ __device__ __forceinline__ void lik_gamma(double y, const double* m, const doubl
 }
 
 // Per-wave LDS scratch of the tensor-rule likelihoods (doubles): Categorical [0,80) exp(f_k(node i)), [80,160) f_k(node i),
-// [160,170) normalised GH weights; Beta [0,80) a_i, psi(a_i), zeta(2,a_i), lgamma(a_i) and the same four for b_j.
+// [160,170) normalised GH weights; Beta [0,80) a_i, psi(a_i), zeta(2,a_i), lgamma(a_i) and the same four for b_j;
+// Student [0,60) r_i = y - f0(node i), f1(node j), s_j = exp(-f1(node j)).
 #define HMOGP_ETAB 176
 
 __device__ __forceinline__ double wave_min(double v) {
@@ -218,6 +220,59 @@ __device__ __forceinline__ void lik_beta_wave(double y, const double* m, const d
     g1 += w * ((pab - pb + l1y) * b);
     h0 += w * ((pab + a * zab - pa - a * za + ly) * a);
     h1 += w * ((pab + b * zab - pb - b * zb + l1y) * b);
+  }
+  o.ve = wave_sum(ve);
+  o.gm[0] = wave_sum(g0);
+  o.gm[1] = wave_sum(g1);
+  o.gv[0] = 0.5 * wave_sum(h0);
+  o.gv[1] = 0.5 * wave_sum(h1);
+}
+
+// ------------------------------------------------------------------------------------------- Student-t, 20 x 20
+// Heteroscedastic Student-t (the reference's student.py is a constructor only): f0 = location (identity link),
+// f1 = log of the squared scale (sigma^2 = exp(f1), HetGaussian's convention), nu = deg_free fixed (the task's lik_param).
+// With r = y - f0, s = exp(min(-f1, LIM_VAL)), u = r^2 s / nu:
+//   log p = C(nu) - f1/2 - (nu+1)/2 log1p(u)
+//   d/df0 = (nu+1) r s / (nu (1+u))          d2/df0^2 = (nu+1) s (u-1) / (nu (1+u)^2)
+//   d/df1 = -1/2 + (nu+1)/2 u/(1+u)          d2/df1^2 = -(nu+1)/2 u/(1+u)^2
+// C(nu) = lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2.  From nu = 64 on the lgamma difference (two numbers of size
+// nu/2 log(nu/2) that cancel to ~log(nu)/2) is its asymptotic series in x = nu/2 instead, truncation error < 1e-16:
+//   lgamma(x + 1/2) - lgamma(x) = log(x)/2 - 1/(8x) + 1/(192x^3) - 1/(640x^5) + 17/(14336x^7) - ...
+// so that C -> -log(2 pi)/2, HetGaussian's constant, without rounding noise of order nu eps.
+__device__ __forceinline__ double student_logc(double nu) {
+  if (nu < 64.0) return lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * log(nu * M_PI);
+  const double ix = 2.0 / nu, z = ix * ix;
+  return -0.5 * log(2.0 * M_PI) + ix * (-1.0 / 8.0 + z * (1.0 / 192.0 + z * (-1.0 / 640.0 + z * (17.0 / 14336.0))));
+}
+
+// 20 x 20 Gauss-Hermite tensor rule, weights w/sqrt(pi) once per dimension: ve = sum w_i w_j log p, dm_d = sum w w d/df_d,
+// dv_d = 1/2 sum w w d2/df_d^2.  The node tables of each dimension (20 + 40 doubles) are formed once per row by 40 lanes in the
+// wave's LDS slice; each of the 400 nodes then costs one log1p and one reciprocal.
+__device__ __forceinline__ void lik_student_wave(double y, const double* m, const double* v, double nu, int lane, double* tab,
+                                                 LikOut& o) {
+  if (lane < 40) {
+    const int dim = lane / 20, i = lane - 20 * dim;
+    const double f = GH20_X[i] * sqrt(2.0 * v[dim]) + m[dim];
+    if (dim == 0) {
+      tab[i] = y - f;
+    } else {
+      tab[20 + i] = f;
+      tab[40 + i] = safe_exp(-f);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();  // written and read by this wave only (LDS operations of a wave are in order)
+  const double c = student_logc(nu), rnu = 1.0 / nu, hn = 0.5 * (nu + 1.0), kn = (nu + 1.0) * rnu;
+  double ve = 0.0, g0 = 0.0, g1 = 0.0, h0 = 0.0, h1 = 0.0;
+  for (int n = lane; n < 400; n += 64) {
+    const int i = n / 20, j = n - 20 * i;
+    const double w = GH20_WN[i] * GH20_WN[j];
+    const double r = tab[i], f1 = tab[20 + j], s = tab[40 + j];
+    const double u = r * r * s * rnu, a = 1.0 / (1.0 + u), ua = u * a;
+    ve += w * (c - 0.5 * f1 - hn * log1p(u));
+    g0 += w * (kn * r * s * a);
+    h0 += w * (kn * s * (u - 1.0) * a * a);
+    g1 += w * (hn * ua - 0.5);
+    h1 += w * (-hn * ua * a);
   }
   o.ve = wave_sum(ve);
   o.gm[0] = wave_sum(g0);
@@ -539,6 +594,9 @@ __device__ __forceinline__ void lik_predictive(const double* m, const double* v,
     a0 = wave_sum(a0), a1 = wave_sum(a1), a2 = wave_sum(a2);
     mean[0] = a0;
     var[0] = a1 + a2 - safe_square(a0);
+  } else if (LIK == HMOGP_LIK_STUDENT) {  // closed form: the moments do not exist for nu <= 1 / nu <= 2
+    mean[0] = param > 1.0 ? m[0] : nan("");
+    var[0] = param > 2.0 ? v[0] + param / (param - 2.0) * safe_exp(m[1] + 0.5 * v[1]) : INFINITY;
   } else {  // Categorical, categorical.py:84-99,224-269: E[rho_d], rho normalised over the K-1 columns; variance zeros
     const int D = (int)param - 1;
     for (int e = lane; e < D * 10; e += 64) {
@@ -590,7 +648,7 @@ __device__ __forceinline__ void lik_predictive(const double* m, const double* v,
 // ============================================================================ Monte-Carlo log predictive
 // log p(y|f) at ONE sample f of q(f), as the reference's `log_predictive` evaluates it (gaussian.py:28-34 -- sigma is
 // ignored, quirk Q6 --, bernoulli.py:31-36, hetgaussian.py:35-39, poisson.py:31-34, exponential.py:28-32,
-// categorical.py:48-63).  Gamma and Beta have no log_predictive in the reference.
+// categorical.py:48-63; Student: the full log p of DESIGN 9).  Gamma and Beta have no log_predictive in the reference.
 template <int LIK>
 __device__ __forceinline__ double lik_logpdf_sample(double y, double yaux, const double* f, double param) {
   if (LIK == HMOGP_LIK_GAUSSIAN) {
@@ -629,6 +687,9 @@ __device__ __forceinline__ double lik_logpdf_sample(double y, double yaux, const
     psum += pK;
     if (label == K) py = pK;
     return log(py / psum);
+  } else if (LIK == HMOGP_LIK_STUDENT) {
+    const double r = y - f[0];
+    return student_logc(param) - 0.5 * f[1] - 0.5 * (param + 1.0) * log1p(r * r * safe_exp(-f[1]) / param);
   }
   return nan("");
 }
@@ -728,6 +789,9 @@ __device__ __forceinline__ double lik_sample(RowRng& g, const double* f, double 
     const double a = clip(safe_exp(f[0]), 1e-9, 1e9), b = clip(safe_exp(f[1]), 1e-9, 1e9);
     const double x = g.gamma(a), yv = g.gamma(b);
     return x / (x + yv);
+  } else if (LIK == HMOGP_LIK_STUDENT) {  // location + scale * t(nu):  z / sqrt(chi2_nu / nu),  chi2_nu = 2 Gamma(nu/2, 1)
+    const double z = g.normal(), G = g.gamma(0.5 * param);
+    return f[0] + safe_exp(0.5 * f[1]) * z * sqrt(param / (2.0 * G));
   } else {  // Categorical: labels 1..K, probabilities clipped then renormalised (categorical.py:66-71)
     const int K = (int)param, D = K - 1;
     double e[HMOGP_MAXJ], esum = 0.0;
@@ -764,11 +828,11 @@ __host__ __device__ constexpr int lik_pred_lanes(int lik) {
 
 // lanes per row of a likelihood
 __host__ __device__ constexpr int lik_lanes(int lik) {
-  return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_CATEGORICAL) ? 64 : 1;
+  return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_STUDENT) ? 64 : 1;
 }
 
 // Dispatch.  For 64-lane likelihoods every lane of the wave must call with the same row; the result is valid in
-// every lane.  `etab` (per-wave LDS, HMOGP_MAXJ*10 doubles) is only used by Categorical.
+// every lane.  `etab` (per-wave LDS, HMOGP_ETAB doubles) is used by the one-wave-per-row likelihoods.
 // CATD: number of functions (K-1) of a Categorical likelihood -- a template parameter so that each K gets its own register
 // allocation (0 for every other likelihood).
 template <int LIK, int CATD = 0>
@@ -784,6 +848,8 @@ __device__ __forceinline__ void lik_eval(double y, double yaux, const double* m,
     lik_gamma(y, m, v, o);
   else if (LIK == HMOGP_LIK_BETA)
     lik_beta_wave(y, m, v, lane, etab, o);
+  else if (LIK == HMOGP_LIK_STUDENT)
+    lik_student_wave(y, m, v, param, lane, etab, o);
   else
     lik_categorical_t<(CATD > 0 ? CATD : 1)>(y, m, v, lane, etab, quirks, o);
   if ((LIK == HMOGP_LIK_GAMMA || LIK == HMOGP_LIK_BETA) && !(quirks & HMOGP_QUIRK_GAMMA_BETA_PI)) {

@@ -392,7 +392,10 @@ __global__ __launch_bounds__(256) void quad_kernel(QuadArgs a) {
 // functions).  One kernel with all fifteen bodies inlined is allocated for the worst of them (256 VGPRs + 32 AGPRs, 380 spilled
 // SGPRs, one wave per SIMD); the sets of the BASELINE configurations get instantiations of their own (C1's
 // {HetGaussian, Bernoulli, Categorical(3)}: see the register table in DESIGN 11e), any other set the all-inclusive one.
-constexpr unsigned qm_bit(int lik, int dimf) { return lik == HMOGP_LIK_CATEGORICAL ? 1u << (8 + dimf) : 1u << lik; }
+// Student (id 8) takes bit 17, above Categorical's 8 + d (d <= 8), so that no bit of an existing family moves.
+constexpr unsigned qm_bit(int lik, int dimf) {
+  return lik == HMOGP_LIK_CATEGORICAL ? 1u << (8 + dimf) : (lik == HMOGP_LIK_STUDENT ? 1u << 17 : 1u << lik);
+}
 constexpr unsigned QM_C1 = qm_bit(HMOGP_LIK_HETGAUSSIAN, 0) | qm_bit(HMOGP_LIK_BERNOULLI, 0) | qm_bit(HMOGP_LIK_CATEGORICAL, 2);
 constexpr unsigned QM_H4 = qm_bit(HMOGP_LIK_GAUSSIAN, 0) | qm_bit(HMOGP_LIK_BERNOULLI, 0) | qm_bit(HMOGP_LIK_POISSON, 0) |
                            qm_bit(HMOGP_LIK_GAMMA, 0);
@@ -434,7 +437,7 @@ __global__ __launch_bounds__(256) void quad_multi_kernel(QuadMulti m) {
     }                                                          \
   }
   QB(HMOGP_LIK_GAUSSIAN) QB(HMOGP_LIK_BERNOULLI) QB(HMOGP_LIK_HETGAUSSIAN) QB(HMOGP_LIK_POISSON) QB(HMOGP_LIK_EXPONENTIAL)
-  QB(HMOGP_LIK_GAMMA) QB(HMOGP_LIK_BETA)
+  QB(HMOGP_LIK_GAMMA) QB(HMOGP_LIK_BETA) QB(HMOGP_LIK_STUDENT)
   QBC(1) QBC(2) QBC(3) QBC(4) QBC(5) QBC(6) QBC(7) QBC(8)
 #undef QB
 #undef QBC
@@ -830,6 +833,7 @@ void launch_sample(int lik, int J, double param, long long N, unsigned long long
     case HMOGP_LIK_EXPONENTIAL: SK(HMOGP_LIK_EXPONENTIAL); break;
     case HMOGP_LIK_GAMMA: SK(HMOGP_LIK_GAMMA); break;
     case HMOGP_LIK_BETA: SK(HMOGP_LIK_BETA); break;
+    case HMOGP_LIK_STUDENT: SK(HMOGP_LIK_STUDENT); break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef SK
@@ -888,6 +892,7 @@ void launch_quad(const QuadArgs& a, hipStream_t s) {
     case HMOGP_LIK_EXPONENTIAL: QK(HMOGP_LIK_EXPONENTIAL); break;
     case HMOGP_LIK_GAMMA: QK(HMOGP_LIK_GAMMA); break;
     case HMOGP_LIK_BETA: QK(HMOGP_LIK_BETA); break;
+    case HMOGP_LIK_STUDENT: QK(HMOGP_LIK_STUDENT); break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef QK
@@ -932,7 +937,7 @@ void launch_quad_multi(const QuadMulti& m_in, hipStream_t s) {
 #define QMS(MASK)                                                                             \
   if ((need & (MASK)) != 0) hipLaunchKernelGGL((quad_multi_kernel<MASK>), dim3(blocks), dim3(256), 0, s, m);
   QMS(QM_LIGHT)
-  QMS(qm_bit(HMOGP_LIK_GAMMA, 0)) QMS(qm_bit(HMOGP_LIK_BETA, 0))
+  QMS(qm_bit(HMOGP_LIK_GAMMA, 0)) QMS(qm_bit(HMOGP_LIK_BETA, 0)) QMS(qm_bit(HMOGP_LIK_STUDENT, 0))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 1)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 2)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 3))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 4)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 5)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 6))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 7)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 8))
@@ -966,6 +971,7 @@ void launch_var_exp(int lik, int J, double param, long long N, const double* y, 
     case HMOGP_LIK_EXPONENTIAL: VK(HMOGP_LIK_EXPONENTIAL); break;
     case HMOGP_LIK_GAMMA: VK(HMOGP_LIK_GAMMA); break;
     case HMOGP_LIK_BETA: VK(HMOGP_LIK_BETA); break;
+    case HMOGP_LIK_STUDENT: VK(HMOGP_LIK_STUDENT); break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef VK
@@ -986,6 +992,7 @@ void launch_predictive(int lik, int J, int Jp, double param, int T, long long N,
     case HMOGP_LIK_EXPONENTIAL: PK(HMOGP_LIK_EXPONENTIAL); break;
     case HMOGP_LIK_GAMMA: PK(HMOGP_LIK_GAMMA); break;
     case HMOGP_LIK_BETA: PK(HMOGP_LIK_BETA); break;
+    case HMOGP_LIK_STUDENT: PK(HMOGP_LIK_STUDENT); break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef PK
@@ -1003,6 +1010,7 @@ void launch_log_predictive(int lik, int J, double param, long long N, int S, uns
     case HMOGP_LIK_CATEGORICAL: LK(HMOGP_LIK_CATEGORICAL); break;
     case HMOGP_LIK_POISSON: LK(HMOGP_LIK_POISSON); break;
     case HMOGP_LIK_EXPONENTIAL: LK(HMOGP_LIK_EXPONENTIAL); break;
+    case HMOGP_LIK_STUDENT: LK(HMOGP_LIK_STUDENT); break;
     default: throw HipError{hipErrorInvalidValue, "the reference defines no log_predictive for this likelihood", __FILE__, __LINE__};
   }
 #undef LK

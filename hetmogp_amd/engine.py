@@ -13,7 +13,7 @@ from ._lib import lib, check
 
 LIK_IDS = dict(Gaussian=_lib.LIK_GAUSSIAN, Bernoulli=_lib.LIK_BERNOULLI, HetGaussian=_lib.LIK_HETGAUSSIAN,
                Categorical=_lib.LIK_CATEGORICAL, Poisson=_lib.LIK_POISSON, Exponential=_lib.LIK_EXPONENTIAL,
-               Gamma=_lib.LIK_GAMMA, Beta=_lib.LIK_BETA)
+               Gamma=_lib.LIK_GAMMA, Beta=_lib.LIK_BETA, Student=_lib.LIK_STUDENT)
 
 
 def _f64(a):
@@ -28,7 +28,7 @@ def lik_dim_f(name, **kw):
     """Number of latent parameter functions (the reference's ``get_metadata()[1]``)."""
     if name == "Categorical":
         return int(kw["K"]) - 1
-    return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2)[name]
+    return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2)[name]
 
 
 def lik_param(name, **kw):
@@ -37,6 +37,8 @@ def lik_param(name, **kw):
         return 0.5 if s is None else float(s)          # gaussian.py:21-24
     if name == "Categorical":
         return float(kw["K"])
+    if name == "Student":
+        return float(kw.get("deg_free", 5.0))          # nu; the library refuses a nu that is not finite and > 0
     return 0.0
 
 

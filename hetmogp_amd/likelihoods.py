@@ -112,6 +112,20 @@ class Beta(_Lik):
         pass
 
 
+class Student(_Lik):
+    """Heteroscedastic Student-t (the reference's likelihoods/student.py is a constructor only; the model is DESIGN 9):
+    f0 = location (identity link), f1 = log of the squared scale (HetGaussian's convention), deg_free = nu fixed.
+    `gp_link` comes first so that the reference's positional call Student(gp_link) still works."""
+    name = "Student"
+    _dims = (1, 2, 1)
+
+    def __init__(self, gp_link=None, deg_free=5.0):
+        self.deg_free = float(deg_free)                    # 5: GPy's StudentT default
+
+    def kwargs(self):
+        return {"deg_free": self.deg_free}
+
+
 class Categorical(_Lik):
     name = "Categorical"
 

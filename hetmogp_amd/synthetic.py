@@ -4,7 +4,7 @@ task's likelihood; inducing inputs on a grid; lengthscale = c * (inducing spacin
 conditioned at large M.  Used by bench.py, smoke() and the size-property tests."""
 import numpy as np
 
-_DIM_F = dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2)
+_DIM_F = dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2)
 
 
 def _dim_f(name, kw):
@@ -40,6 +40,9 @@ def _sample(rng, name, kw, F):
         return rng.gamma(np.exp(np.clip(F[:, :1], -2, 2)), 1.0 / np.exp(np.clip(F[:, 1:2], -2, 2))) + 1e-6
     if name == "Beta":
         return np.clip(rng.beta(np.exp(np.clip(F[:, :1], -2, 2)), np.exp(np.clip(F[:, 1:2], -2, 2))), 1e-6, 1 - 1e-6)
+    if name == "Student":
+        nu = kw.get("deg_free", 5.0)
+        return F[:, :1] + np.exp(0.5 * F[:, 1:2]) * rng.standard_t(nu, (n, 1))
     if name == "Categorical":
         K = kw["K"]
         e = np.exp(F[:, :K - 1])

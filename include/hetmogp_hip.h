@@ -42,7 +42,8 @@ enum {
   HMOGP_LIK_POISSON = 4,     /* poisson.py                                            dim_f = 1   */
   HMOGP_LIK_EXPONENTIAL = 5, /* exponential.py                                        dim_f = 1   */
   HMOGP_LIK_GAMMA = 6,       /* gamma.py                                              dim_f = 2   */
-  HMOGP_LIK_BETA = 7         /* beta.py                                               dim_f = 2   */
+  HMOGP_LIK_BETA = 7,        /* beta.py                                               dim_f = 2   */
+  HMOGP_LIK_STUDENT = 8      /* student.py      param = deg_free nu (finite, > 0)     dim_f = 2   */
 };
 
 /* error codes; the Python facade maps them onto the reference's exception types */
@@ -356,7 +357,9 @@ int hmogp_potrs_rows(int32_t device, const double* L, int32_t M, const double* B
 int hmogp_gemm_f64(int32_t device, int32_t transA, int32_t transB, int32_t M, int32_t N, int32_t K,
                    double alpha, const double* A, int32_t lda, const double* B, int32_t ldb, double beta,
                    double* C, int32_t ldc);
-/* Variational expectations of one likelihood: y [N], m,v [N, dim_f] -> ve [N], dm, dv [N, dim_f].         */
+/* Variational expectations of one likelihood: y [N], m,v [N, dim_f] -> ve [N], dm, dv [N, dim_f].
+ * Here and in hmogp_predictive / hmogp_log_predictive / hmogp_sample / hmogp_create a Student deg_free that is not
+ * finite and > 0 is HMOGP_E_INVALID.                                                                      */
 int hmogp_var_exp(int32_t device, int32_t lik_id, double lik_param, int64_t N, const double* y,
                   const double* m, const double* v, double* ve, double* dm, double* dv);
 
@@ -376,7 +379,8 @@ int hmogp_predictive(int32_t device, int32_t lik_id, double lik_param, int32_t g
  * bernoulli.py:130-144): log_pred[n] = -log(S) + logsumexp_s log p(y_n | f_s), f_s ~ N(m_n, diag v_n), S = num_samples,
  * counter-based generator seeded by `seed` (reproducible; a different stream than NumPy's).  The reference then returns
  * (1/S) * sum_n log_pred[n] and HetLikelihood.negative_log_predictive (het_likelihood.py:150-164) negates the sum over
- * tasks -- done by the caller.  Defined for Gaussian, Bernoulli, HetGaussian, Poisson, Exponential, Categorical.   */
+ * tasks -- done by the caller.  Defined for Gaussian, Bernoulli, HetGaussian, Poisson, Exponential, Categorical,
+ * Student.                                                                                                     */
 int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64_t N, int32_t num_samples, uint64_t seed,
                          const double* y, const double* m, const double* v, double* log_pred);
 

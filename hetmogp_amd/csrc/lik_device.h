@@ -287,7 +287,7 @@ __device__ __forceinline__ void lik_student_wave(double y, const double* m, cons
 // table holds exp(f_k(node i)) and f_k(node i), [D][10] each.  The LAST min(D,3) dimensions are strided over the lanes
 // (their digits, table entries and weight product are formed once per lane and chunk); the remaining leading dimensions
 // are a uniform outer loop.  A node whose probabilities are not touched by the reference's clip to [1e-9, 1-1e-9] takes
-//   log p_y = f_y - log(den),  d2 = -p_d (den - e_d)/den      (one reciprocal, one log per node)
+//   log p_y = f_y - log(den),  d2 = -p_d (1 + sum_{j != d} e_j)/den      (one reciprocal, one log per node)
 // which equals the reference's clipped / renormalised expressions to rounding; any other node (clip active, overflow)
 // takes the literal formulas.
 template <int D>
@@ -322,6 +322,25 @@ __device__ __forceinline__ void cat_node_literal(const double (&e)[D], double w,
   }
 }
 
+// rest_d = den - e_d = 1 + sum_{j != d} e_j, formed by prefix and suffix sums and never by the subtraction: where one function
+// dominates (e_d >> 1 + the others) den - e_d cancels to nothing in float64, while the reference adds e_d + sum_j e^{f_j + f_d}
+// and loses no digit.  SKIP >= 0 leaves function SKIP out of the sums (the register dimension, added by the caller).
+template <int D, int SKIP = -1>
+__device__ __forceinline__ void cat_rest(const double (&e)[D], double (&rest)[D]) {
+  double pre = 1.0;
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    rest[d] = pre;
+    if (d != SKIP) pre += e[d];
+  }
+  double suf = 0.0;
+#pragma unroll
+  for (int d = D - 1; d >= 0; --d) {
+    if (d < D - 1) rest[d] += suf;
+    if (d != SKIP) suf += e[d];
+  }
+}
+
 // One node whose probabilities ARE touched by the clip, denominators far from overflow (den < 1e150): the literal formulas
 // with every division replaced by a multiplication with a Newton-refined reciprocal and the library log by fast_log_pos
 // (<= 2 ulp away from the reference's IEEE divisions; a clip comparison can only flip for a value within an ulp of the bound).
@@ -341,24 +360,28 @@ __device__ __forceinline__ void cat_node_clipped(const double (&e)[D], double de
   psum += pK;
   if (label == K) py = pK;
   ve = fma(w, fast_log_pos(py) - fast_log_pos(psum), ve);
+  double rest[D];
+  cat_rest<D>(e, rest);
 #pragma unroll
-  for (int d = 0; d < D; ++d) {   // (e_d + sum_{j != d} e_j e_d) / den^2 = e_d (den - e_d) / den^2, no overflow below 1e150
+  for (int d = 0; d < D; ++d) {   // (e_d + sum_{j != d} e_j e_d) / den^2 = e_d (1 + sum_{j != d} e_j) / den^2, no overflow below 1e150
     const double pd = e[d] * rden;
-    hv[d] = fma(w * pd, (den - e[d]) * rden, hv[d]);
+    hv[d] = fma(w * pd, rest[d] * rden, hv[d]);
     if (exact_dm) gx[d] = fma(w, (label == d + 1 ? 1.0 : 0.0) - pd, gx[d]);
   }
 }
 
-// One node on the "clip inactive" path: log p_y = f_y - log(den), d2 log p / df_d^2 = -p_d (den - e_d) / den.
+// One node on the "clip inactive" path: log p_y = f_y - log(den), d2 log p / df_d^2 = -p_d (1 + sum_{j != d} e_j) / den.
 template <int D>
 __device__ __forceinline__ void cat_node_fast(const double (&e)[D], double den, double w, double fy, int label, bool exact_dm,
                                               double& ve, double (&hv)[D], double (&gx)[D]) {
   const double rden = fast_rcp_pos(den);
   ve = fma(w, fy - fast_log_pos(den), ve);
+  double rest[D];
+  cat_rest<D>(e, rest);
 #pragma unroll
   for (int d = 0; d < D; ++d) {
     const double pd = e[d] * rden;
-    hv[d] = fma(w * pd, (den - e[d]) * rden, hv[d]);
+    hv[d] = fma(w * pd, rest[d] * rden, hv[d]);
     if (exact_dm) gx[d] = fma(w, (label == d + 1 ? 1.0 : 0.0) - pd, gx[d]);
   }
 }
@@ -460,11 +483,12 @@ __device__ __forceinline__ void lik_categorical_t(double y, const double* m, con
         }
         if (all_fast) {
           // Ten fast-path nodes that differ in the register dimension only.  For every OTHER dimension d the entry e_d is the
-          // same in all ten, so  sum_i w_i p_di (1 - p_di) = e_d (A - e_d B)  with  A = sum_i w_i / den_i,
-          // B = sum_i w_i / den_i^2  (and sum_i w_i (delta - p_di) = delta W - e_d A): two running sums per node instead
-          // of five operations per node and dimension.  (Cancellation only where p_d -> 1, i.e. where the terms themselves
-          // vanish against the total; the fast path is only entered for 1e-9 <= p <= 1 - 1e-9.)
-          double A = 0.0, B = 0.0, Wt = 0.0;
+          // same in all ten and den_i - e_d = rest_d + er_i with rest_d = 1 + the entries of the remaining dimensions, so
+          //   sum_i w_i p_di (1 - p_di) = e_d (rest_d B + C),  B = sum_i w_i / den_i^2,  C = sum_i w_i er_i / den_i^2
+          // (all terms positive: no cancellation where one function dominates), and for the register dimension itself
+          // den_i - er_i = 1 + ss:  sum_i w_i p_i (1 - p_i) = (1 + ss) C.  sum_i w_i (delta - p_di) = delta W - e_d A with
+          // A = sum_i w_i / den_i.  Three running sums per node instead of five operations per node and dimension.
+          double A = 0.0, B = 0.0, Cs = 0.0, Wt = 0.0;
 #pragma unroll
           for (int i = 0; i < 10; ++i) {
             const double den = 1.0 + (ss + er[i]), w = ws * wr[i];
@@ -472,17 +496,20 @@ __device__ __forceinline__ void lik_categorical_t(double y, const double* m, con
             ve = fma(w, (fys + fr[i]) - fast_log_pos(den), ve);
             const double w1 = w * rden, w2 = w1 * rden;
             A += w1, B += w2;
-            hv[RD] = fma(w2, er[i] * (den - er[i]), hv[RD]);
+            Cs = fma(w2, er[i], Cs);
             if (exact_dm) {
               Wt += w;
               gx[RD] = fma(-w1, er[i], gx[RD]);
             }
           }
+          hv[RD] = fma(1.0 + ss, Cs, hv[RD]);
           if (exact_dm && label == RD + 1) gx[RD] += Wt;
+          double rest[D];
+          cat_rest<D, RD>(e, rest);
 #pragma unroll
           for (int d = 0; d < D; ++d) {
             if (d == RD) continue;
-            hv[d] = fma(e[d], fma(-e[d], B, A), hv[d]);
+            hv[d] = fma(e[d], fma(rest[d], B, Cs), hv[d]);
             if (exact_dm) gx[d] += (label == d + 1 ? Wt : 0.0) - e[d] * A;
           }
         } else {

@@ -14,8 +14,10 @@ ABI_VERSION = 8
 # likelihood ids (class names of the reference's likelihoods/<name>.py)
 LIK_GAUSSIAN, LIK_BERNOULLI, LIK_HETGAUSSIAN, LIK_CATEGORICAL, LIK_POISSON, LIK_EXPONENTIAL, LIK_GAMMA, LIK_BETA = range(8)
 LIK_STUDENT = 8          # heteroscedastic Student-t (the reference's likelihoods/student.py stub)
+LIK_ORDINAL = 9          # ordered probit (the reference's likelihoods/ordinal.py stub); lik_param = hmogp_ordinal_table id
+ORDINAL_MAXK = 32
 LIK_IDS_BY_NAME = dict(Gaussian=0, Bernoulli=1, HetGaussian=2, Categorical=3, Poisson=4, Exponential=5, Gamma=6, Beta=7,
-                       Student=8)
+                       Student=8, Ordinal=9)
 E_INVALID, E_NO_DEVICE, E_NOT_PD, E_SQI_UNSTABLE, E_STATE, E_COMM = -1, -2, -3, -4, -5, -6
 NTIMINGS = 11
 COMM_ID_BYTES = 128
@@ -117,6 +119,7 @@ EXPORTS = {
     "hmogp_potrs_rows": (C.c_int, [C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int64, c_double_p]),
     "hmogp_gemm_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_double_p,
                                  C.c_int32, c_double_p, C.c_int32, C.c_double, c_double_p, C.c_int32]),
+    "hmogp_ordinal_table": (C.c_int, [C.c_int32, c_double_p, C.c_double, c_double_p]),
     "hmogp_predictive": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, c_double_p, c_double_p, c_double_p,
                                    c_double_p]),
     "hmogp_log_predictive": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_uint64, c_double_p,

@@ -37,6 +37,20 @@ void need_device(int device) {
   HIP_TRY(hipSetDevice(device));
 }
 
+// y [N] of a building block -> device.  Ordinal: the labels are checked and replaced by the rows' lower, then upper cut points
+// ([2][N], what launch_var_exp / launch_log_predictive read), so that the device code is the engine's.
+void upload_y(int lik_id, double lik_param, const double* y, long long N, DevBuf& dy) {
+  if (lik_id != HMOGP_LIK_ORDINAL) {
+    dy.ensure(sizeof(double) * N);
+    HIP_TRY(hipMemcpy(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice));
+    return;
+  }
+  std::vector<double> cuts(2 * (size_t)N);
+  ordinal_row_cuts(ordinal_table(lik_param), y, N, cuts.data(), cuts.data() + N);
+  dy.ensure(sizeof(double) * 2 * N);
+  HIP_TRY(hipMemcpy(dy.p, cuts.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
+}
+
 }  // namespace
 
 extern "C" {
@@ -431,9 +445,9 @@ int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t 
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !y || !m || !v || !ve || !dm || !dv)
       throw EngineError{HMOGP_E_INVALID, "bad arguments"};
     DevBuf dy, dmm, dvv, dve, ddm, ddv;
-    dy.ensure(sizeof(double) * N), dve.ensure(sizeof(double) * N);
+    upload_y(lik_id, lik_param, y, N, dy);
+    dve.ensure(sizeof(double) * N);
     for (DevBuf* b : {&dmm, &dvv, &ddm, &ddv}) b->ensure(sizeof(double) * N * J);
-    HIP_TRY(hipMemcpy(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dmm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dvv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
     launch_var_exp(lik_id, J, lik_param, N, dy.d(), dmm.d(), dvv.d(), dve.d(), ddm.d(), ddv.d(), nullptr, quirks);
@@ -441,6 +455,13 @@ int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t 
     HIP_TRY(hipMemcpy(ve, dve.p, sizeof(double) * N, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(dm, ddm.p, sizeof(double) * N * J, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(dv, ddv.p, sizeof(double) * N * J, hipMemcpyDeviceToHost));
+  });
+}
+
+int hmogp_ordinal_table(int32_t K, const double* edges, double sigma, double* lik_param_out) {
+  return guarded(nullptr, [&] {
+    if (!lik_param_out) throw EngineError{HMOGP_E_INVALID, "lik_param_out is NULL"};
+    *lik_param_out = ordinal_register(K, edges, sigma);
   });
 }
 
@@ -478,9 +499,9 @@ int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64
     if (lik_id == HMOGP_LIK_GAMMA || lik_id == HMOGP_LIK_BETA)
       throw EngineError{HMOGP_E_INVALID, "the reference defines no log_predictive for Gamma / Beta"};
     DevBuf dy, dm, dv, dout;
-    dy.ensure(sizeof(double) * N), dout.ensure(sizeof(double) * N);
+    upload_y(lik_id, lik_param, y, N, dy);
+    dout.ensure(sizeof(double) * N);
     dm.ensure(sizeof(double) * N * J), dv.ensure(sizeof(double) * N * J);
-    HIP_TRY(hipMemcpy(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
     launch_log_predictive(lik_id, J, lik_param, N, num_samples, seed, dy.d(), dm.d(), dv.d(), dout.d(), nullptr);

@@ -137,6 +137,7 @@ void hmogp_engine::init(const hmogp_config* c) {
     if (k.lik == HMOGP_LIK_GAUSSIAN && !(k.param > 0.0)) k.param = 0.5;  // gaussian.py:21-24
     k.dimf = lik_dimf(k.lik, k.param);
     check_lik_param(k.lik, k.param);
+    k.qparam = k.lik == HMOGP_LIK_ORDINAL ? ordinal_table(k.param).sigma : k.param;
     if (k.dimf < 1 || k.dimf > HMOGP_MAXJ) throw EngineError{HMOGP_E_INVALID, "unsupported likelihood / dim_f"};
     k.d0 = d;
     for (int j = 0; j < k.dimf; ++j, ++d)
@@ -197,6 +198,11 @@ void hmogp_engine::init(const hmogp_config* c) {
 void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long long N) {
   if (t < 0 || t >= T || N < 0 || (N > 0 && (!X || !Y))) throw EngineError{HMOGP_E_INVALID, "bad task data"};
   Task& k = tasks[t];
+  std::vector<double> cuts;
+  if (k.lik == HMOGP_LIK_ORDINAL && N > 0) {  // the rows' own cut points depend on the data only; a label that is not an integer in
+    cuts.resize(2 * (size_t)N);               // 1..K is refused before the task's state changes
+    ordinal_row_cuts(ordinal_table(k.param), Y, N, cuts.data(), cuts.data() + N);
+  }
   k.N = N;
   began = false;
   staged_key.clear();
@@ -210,6 +216,11 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
     k.Yaux.ensure(sizeof(double) * N);
     launch_gammaln1p(k.Y.d(), k.Yaux.d(), N, st);
     HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (k.lik == HMOGP_LIK_ORDINAL) {
+    k.Ylo.ensure(sizeof(double) * N), k.Yaux.ensure(sizeof(double) * N);
+    HIP_TRY(hipMemcpy(k.Ylo.p, cuts.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k.Yaux.p, cuts.data() + N, sizeof(double) * N, hipMemcpyHostToDevice));
   }
 }
 

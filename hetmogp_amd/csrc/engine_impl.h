@@ -100,14 +100,22 @@ static_assert(NCAT == HMOGP_NTIMINGS, "hmogp_last_timings layout");
 struct Task {
   long long N = 0;
   DevBuf X, Y, Yaux;
+  DevBuf Ylo;      // Ordinal: the rows' lower cut points (Yaux holds the upper ones, Y keeps the labels)
   int lik = 0, dimf = 1, d0 = 0;
   double param = 0.0;
+  double qparam = 0.0;   // what the quadrature kernels get as lik_param: `param`, but sigma for Ordinal (whose param is a table id)
+  const double* quad_y() const { return lik == HMOGP_LIK_ORDINAL ? Ylo.d() : Y.d(); }   // first per-row value of the quadrature
   DevBuf offsets;  // device: quad scalar slot -> bundle offset
   int nscal = 0;
 };
 
 int lik_dimf(int lik, double param);
-void check_lik_param(int lik, double param);  // HMOGP_E_INVALID for a parameter the likelihood has no value for (Student: nu)
+void check_lik_param(int lik, double param);  // HMOGP_E_INVALID for a parameter the likelihood has no value for (Student: nu;
+                                              // Ordinal: an id hmogp_ordinal_table never returned)
+// Ordinal: labels y [N] (integers in 1..K, else HMOGP_E_INVALID) -> the rows' lower / upper cut points (-inf / +inf at the ends)
+void ordinal_row_cuts(const OrdinalTable& tb, const double* y, long long N, double* lo, double* hi);
+// registers (or finds) a table; returns the value to pass as lik_param
+double ordinal_register(int K, const double* edges, double sigma);
 
 // Row ranges per weighted-Gram launch: a multiple of 8 (one range per XCD at a time), each >= 32 k-steps of 16 rows,
 // enough blocks (lower tiles x ranges) for >= 8 rounds over the 256 CUs, at most KS_MAX slabs.

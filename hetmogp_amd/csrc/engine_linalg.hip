@@ -3,6 +3,9 @@
 // Split out of engine.hip in round 6 (no behaviour change); declarations: engine_impl.h.
 #include "engine_impl.h"
 
+#include <memory>
+#include <mutex>
+
 namespace hmogp_detail {
 
 int lik_dimf(int lik, double param) {
@@ -10,7 +13,8 @@ int lik_dimf(int lik, double param) {
     case HMOGP_LIK_GAUSSIAN:
     case HMOGP_LIK_BERNOULLI:
     case HMOGP_LIK_POISSON:
-    case HMOGP_LIK_EXPONENTIAL: return 1;
+    case HMOGP_LIK_EXPONENTIAL:
+    case HMOGP_LIK_ORDINAL: return 1;
     case HMOGP_LIK_HETGAUSSIAN:
     case HMOGP_LIK_GAMMA:
     case HMOGP_LIK_BETA:
@@ -23,6 +27,48 @@ int lik_dimf(int lik, double param) {
 void check_lik_param(int lik, double param) {
   if (lik == HMOGP_LIK_STUDENT && !(std::isfinite(param) && param > 0.0))
     throw EngineError{HMOGP_E_INVALID, "Student: deg_free must be finite and > 0"};
+  if (lik == HMOGP_LIK_ORDINAL) (void)ordinal_table(param);
+}
+
+// ------------------------------------------------------------------------------------ Ordinal tables
+// Every entry point carries one double per task; an Ordinal task needs K numbers.  They are registered once, in a process-wide
+// append-only registry, and the id (1, 2, ...) travels as lik_param.  Entries are heap-allocated and never freed or moved, so a
+// reference handed out stays valid without the lock.
+namespace {
+std::mutex g_ord_mutex;
+std::vector<std::unique_ptr<OrdinalTable>> g_ord_tables;
+}  // namespace
+
+double ordinal_register(int K, const double* edges, double sigma) {
+  if (K < 2 || K > HMOGP_ORDINAL_MAXK) throw EngineError{HMOGP_E_INVALID, "Ordinal: 2 <= K <= HMOGP_ORDINAL_MAXK"};
+  if (!edges) throw EngineError{HMOGP_E_INVALID, "Ordinal: edges is NULL"};
+  if (!(std::isfinite(sigma) && sigma > 0.0)) throw EngineError{HMOGP_E_INVALID, "Ordinal: sigma must be finite and > 0"};
+  for (int k = 0; k < K - 1; ++k)
+    if (!std::isfinite(edges[k]) || (k > 0 && !(edges[k] > edges[k - 1])))
+      throw EngineError{HMOGP_E_INVALID, "Ordinal: the cut points must be finite and strictly increasing"};
+  std::lock_guard<std::mutex> lock(g_ord_mutex);
+  for (size_t i = 0; i < g_ord_tables.size(); ++i) {
+    const OrdinalTable& t = *g_ord_tables[i];
+    if (t.K == K && t.sigma == sigma && std::equal(edges, edges + (K - 1), t.edge)) return (double)(i + 1);
+  }
+  if (g_ord_tables.size() >= HMOGP_ORDINAL_MAXTABLES)
+    throw EngineError{HMOGP_E_INVALID, "Ordinal: HMOGP_ORDINAL_MAXTABLES distinct tables are registered already"};
+  std::unique_ptr<OrdinalTable> t(new OrdinalTable());
+  t->K = K, t->sigma = sigma;
+  for (int k = 0; k < HMOGP_ORDINAL_MAXK - 1; ++k) t->edge[k] = k < K - 1 ? edges[k] : INFINITY;
+  g_ord_tables.push_back(std::move(t));
+  return (double)g_ord_tables.size();
+}
+
+void ordinal_row_cuts(const OrdinalTable& tb, const double* y, long long N, double* lo, double* hi) {
+  for (long long n = 0; n < N; ++n) {
+    const double l = y[n];
+    if (!(l >= 1.0 && l <= (double)tb.K && l == std::floor(l)))
+      throw EngineError{HMOGP_E_INVALID, "Ordinal: a label is not an integer in 1..K"};
+    const int k = (int)l;
+    lo[n] = k == 1 ? -INFINITY : tb.edge[k - 2];
+    hi[n] = k == tb.K ? INFINITY : tb.edge[k - 1];
+  }
 }
 
 int gram_ksplit(long long n, int M) {
@@ -237,3 +283,11 @@ bool potrs_rows_inplace(double* V, long long sV, const double* Luu, long long sL
 }
 
 }  // namespace hmogp_detail
+
+// (global scope: declared in rowpass.h, which the kernel launchers share)
+const OrdinalTable& ordinal_table(double lik_param) {
+  std::lock_guard<std::mutex> lock(hmogp_detail::g_ord_mutex);
+  if (!(lik_param >= 1.0 && lik_param <= (double)hmogp_detail::g_ord_tables.size() && lik_param == std::floor(lik_param)))
+    throw hmogp_detail::EngineError{HMOGP_E_INVALID, "Ordinal: lik_param is not an id returned by hmogp_ordinal_table"};
+  return *hmogp_detail::g_ord_tables[(size_t)lik_param - 1];
+}

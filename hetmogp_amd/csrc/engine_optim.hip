@@ -66,8 +66,8 @@ void hmogp_engine::debug_raw(double* o_kmm, double* o_kmn, double* o_kdiag) {
     Task& k = tasks[sg.t];
     gmt[sg.t].ensure(sizeof(double) * nt[sg.t] * k.dimf), gvt[sg.t].ensure(sizeof(double) * nt[sg.t] * k.dimf);
     QuadArgs qa;
-    qa.lik = k.lik, qa.lik_param = k.param, qa.dimf = k.dimf, qa.Q = Q, qa.N = sg.n;
-    qa.y = k.Y.d() + sg.r0;
+    qa.lik = k.lik, qa.lik_param = k.qparam, qa.dimf = k.dimf, qa.Q = Q, qa.N = sg.n;
+    qa.y = k.quad_y() + sg.r0;
     qa.yaux = k.Yaux.p ? k.Yaux.d() + sg.r0 : nullptr;
     qa.p = vp.d() + sg.off, qa.c = vc.d() + sg.off, qa.pt = vpt.d() + sg.off, qa.ct = vct.d() + sg.off;
     qa.ldn = ldn;

@@ -420,8 +420,8 @@ void hmogp_engine::row_pass() {
     auto quad_segment = [&](const Seg& sg) {
       Task& k = tasks[sg.t];
       QuadArgs qa;
-      qa.lik = k.lik, qa.lik_param = k.param, qa.dimf = k.dimf, qa.Q = Q, qa.N = sg.n;
-      qa.y = k.Y.d() + sg.r0;
+      qa.lik = k.lik, qa.lik_param = k.qparam, qa.dimf = k.dimf, qa.Q = Q, qa.N = sg.n;
+      qa.y = k.quad_y() + sg.r0;
       qa.yaux = k.Yaux.p ? k.Yaux.d() + sg.r0 : nullptr;
       qa.p = vp.d() + sg.off, qa.c = vc.d() + sg.off;
       const bool row_sl = want_hyper && !col_sl;    // (small-model / strict paths: sl from the row statistics p~, c~)
@@ -553,8 +553,8 @@ void hmogp_engine::row_pass() {
         const Seg& sg = pl[i];
         Task& k = tasks[sg.t];
         QuadSeg& g = qm.seg[i];
-        g.lik = k.lik, g.dimf = k.dimf, g.d0 = k.d0, g.t = sg.t, g.lik_param = k.param, g.N = sg.n, g.off = sg.off;
-        g.y = k.Y.d() + sg.r0, g.yaux = k.Yaux.p ? k.Yaux.d() + sg.r0 : nullptr;
+        g.lik = k.lik, g.dimf = k.dimf, g.d0 = k.d0, g.t = sg.t, g.lik_param = k.qparam, g.N = sg.n, g.off = sg.off;
+        g.y = k.quad_y() + sg.r0, g.yaux = k.Yaux.p ? k.Yaux.d() + sg.r0 : nullptr;
         auto& r = qred.s[qred.nseg++];
         r.part = quadpart.d() + part, r.nrows = quad_blocks(k.lik, sg.n), r.nscal = k.nscal, r.off = k.offsets.as<long long>();
         part += r.nrows * k.nscal;

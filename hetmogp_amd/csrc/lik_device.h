@@ -1,7 +1,8 @@
 // lik_device.h -- device-side variational expectations E_q(f)[log p(y|f)] and their derivatives with respect to
 // the mean / variance of q(f), for the eight likelihoods of /root/reference/likelihoods/*.py (SURVEY.md 8a, rows
-// L1-L8) and the heteroscedastic Student-t the reference only stubs (student.py; contract: DESIGN 9).  Results
-// reproduce the reference's formulas including its clips and quirks:
+// L1-L8), the heteroscedastic Student-t the reference only stubs (student.py; contract: DESIGN 9) and the Ordinal (ordered
+// probit) likelihood it only stubs as well (ordinal.py; contract: DESIGN 9b; no clip).  Results reproduce the reference's formulas
+// including its clips and quirks:
 //   Q1  Gamma / Beta: Gauss-Hermite weights divided by sqrt(pi) twice (gamma.py:110,139-141; beta.py:113,142-144)
 //   Q2  Categorical: d/dm is the constant onehot(y)[d] - 1 (categorical.py:102-113)
 // Lane mapping: closed forms, 1-D quadratures and Gamma (separable in its two functions) use ONE lane per row;
@@ -144,6 +145,80 @@ __device__ __forceinline__ void lik_gamma(double y, const double* m, const doubl
   o.gm[1] = S0 * A1 - y * S0 * B1;
   o.gv[0] = 0.5 * (-S0 * (Apsi + Azeta) + common);
   o.gv[1] = 0.5 * (-y * S0 * B1);
+}
+
+// ------------------------------------------------------------------------------------------- Ordinal (ordered probit), T = 20
+// DESIGN 9b (the reference's ordinal.py is a constructor only).  One node of the rule: with a = (lo - f) / sigma < b = (hi - f) / sigma
+// the row's own two cut points seen from f (one of them may be infinite), P = Phi(b) - Phi(a) and phi the normal density,
+//   lp = log P,   g = (phi(a) - phi(b)) / P,   h = (a phi(a) - b phi(b)) / P       (terms with an infinite a or b are 0)
+// without a clip and without ever forming a P that underflows:
+//   * mirror (a, b) -> (-b, -a) when the bin lies on the upper side, so that |b| <= |a| and a < 0; g changes sign, lp and h do not;
+//   * the bin straddles f (b > 0) and the two tails Q = Phi(a) + Phi(-b) hold less than half: lp = log1p(-Q), P = 1 - Q >= 1/2;
+//   * otherwise, with E(x) = erfcx(-x / sqrt 2) and d = (a^2 - b^2) / 2 >= 0:  P = exp(-b^2 / 2) D / 2,  D = E(b) - exp(-d) E(a), so
+//       lp = -b^2 / 2 + log(D / 2),   g = sqrt(2 / pi) expm1(-d) / D,   h = sqrt(2 / pi) (a exp(-d) - b) / D,
+//     D being formed as (E(b) - E(a)) - expm1(-d) E(a), a sum of two positive numbers.
+// An end bin costs one erfcx (E(-inf) = 0), a middle bin two.  What is left is the cancellation of a NARROW bin in E(b) - E(a),
+// measured in DESIGN 9b.
+#define ORD_INV_SQRT_2PI 0.3989422804014327
+#define ORD_SQRT_2_OVER_PI 0.7978845608028654
+__device__ __forceinline__ void ordinal_node(double a, double b, double& lp, double& g, double& h) {
+  double sgn = 1.0;
+  if (a + b > 0.0) {
+    const double t = a;
+    a = -b, b = -t, sgn = -1.0;
+  }
+  if (b > 0.0) {
+    const double Q = 0.5 * (erfc(-a * M_SQRT1_2) + erfc(b * M_SQRT1_2));
+    if (Q < 0.5) {
+      const double rP = 1.0 / (1.0 - Q);
+      const double pa = ORD_INV_SQRT_2PI * exp(-0.5 * a * a), pb = ORD_INV_SQRT_2PI * exp(-0.5 * b * b);
+      lp = log1p(-Q);
+      g = sgn * (pa - pb) * rP;
+      h = ((isinf(a) ? 0.0 : a * pa) - (isinf(b) ? 0.0 : b * pb)) * rP;
+      return;
+    }
+  }
+  const double Ea = erfcx(-a * M_SQRT1_2), Eb = erfcx(-b * M_SQRT1_2);  // a = -inf: E = 0
+  const double em = expm1(0.5 * (b - a) * (a + b));                      //           expm1(-inf) = -1
+  const double D = (Eb - Ea) - em * Ea;
+  const double rD = ORD_SQRT_2_OVER_PI / D;
+  lp = -0.5 * b * b + log(0.5 * D);
+  g = sgn * em * rD;
+  h = ((isinf(a) ? 0.0 : a * (1.0 + em)) - b) * rD;
+}
+
+// 20-node rule, one lane per row: ve = sum w log p, dm = sum w dlog p/df, dv = 1/2 sum w d2log p/df2 with
+// dlog p/df = g / sigma, d2log p/df2 = h / sigma^2 - (dlog p/df)^2.
+__device__ __forceinline__ void lik_ordinal(double lo, double hi, double m, double v, double sigma, LikOut& o) {
+  const double s = sqrt(2.0 * v), s2 = sigma * sigma;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma unroll 1
+  for (int i = 0; i < 20; ++i) {
+    const double f = GH20_X[i] * s + m, w = GH20_WN[i];
+    double lp, g, h;
+    ordinal_node((lo - f) / sigma, (hi - f) / sigma, lp, g, h);
+    const double d1 = g / sigma;
+    a0 += lp * w;
+    a1 += d1 * w;
+    a2 += (h / s2 - d1 * d1) * w;
+  }
+  o.ve = a0;
+  o.gm[0] = a1;
+  o.gv[0] = 0.5 * a2;
+}
+
+// closed-form moments of the label under q(f) = N(m, v): with z_k = (b_k - m) / sqrt(sigma^2 + v), P(y > k) = Phi(-z_k), so
+// mean = 1 + sum_k Phi(-z_k) and E[y^2] = 1 + sum_k (2 k + 1) Phi(-z_k), k = 1 .. K - 1: sums of positive terms.
+__device__ __forceinline__ void lik_ordinal_predictive(const OrdinalTable& tb, double m, double v, double& mean, double& var) {
+  const double rs = M_SQRT1_2 / sqrt(tb.sigma * tb.sigma + v);
+  double e1 = 1.0, e2 = 1.0;
+  for (int k = 0; k < tb.K - 1; ++k) {
+    const double q = 0.5 * erfc((tb.edge[k] - m) * rs);
+    e1 += q;
+    e2 += (double)(2 * k + 3) * q;
+  }
+  mean = e1;
+  var = e2 - e1 * e1;
 }
 
 // Per-wave LDS scratch of the tensor-rule likelihoods (doubles): Categorical [0,80) exp(f_k(node i)), [80,160) f_k(node i),
@@ -675,7 +750,8 @@ __device__ __forceinline__ void lik_predictive(const double* m, const double* v,
 // ============================================================================ Monte-Carlo log predictive
 // log p(y|f) at ONE sample f of q(f), as the reference's `log_predictive` evaluates it (gaussian.py:28-34 -- sigma is
 // ignored, quirk Q6 --, bernoulli.py:31-36, hetgaussian.py:35-39, poisson.py:31-34, exponential.py:28-32,
-// categorical.py:48-63; Student: the full log p of DESIGN 9).  Gamma and Beta have no log_predictive in the reference.
+// categorical.py:48-63; Student: the full log p of DESIGN 9; Ordinal: the un-clipped log p of DESIGN 9b, y / yaux = the row's
+// lower / upper cut point and param = sigma as in the quadrature).  Gamma and Beta have no log_predictive in the reference.
 template <int LIK>
 __device__ __forceinline__ double lik_logpdf_sample(double y, double yaux, const double* f, double param) {
   if (LIK == HMOGP_LIK_GAUSSIAN) {
@@ -717,6 +793,10 @@ __device__ __forceinline__ double lik_logpdf_sample(double y, double yaux, const
   } else if (LIK == HMOGP_LIK_STUDENT) {
     const double r = y - f[0];
     return student_logc(param) - 0.5 * f[1] - 0.5 * (param + 1.0) * log1p(r * r * safe_exp(-f[1]) / param);
+  } else if (LIK == HMOGP_LIK_ORDINAL) {
+    double lp, g, h;
+    ordinal_node((y - f[0]) / param, (yaux - f[0]) / param, lp, g, h);
+    return lp;
   }
   return nan("");
 }
@@ -848,6 +928,14 @@ __device__ __forceinline__ double lik_sample(RowRng& g, const double* f, double 
   }
 }
 
+// Ordinal: y = 1 + #{k : f + sigma eps > b_k}, eps ~ N(0, 1)
+__device__ __forceinline__ double lik_ordinal_sample(RowRng& g, const OrdinalTable& tb, double f) {
+  const double z = f + tb.sigma * g.normal();
+  int label = 1;
+  for (int k = 0; k < tb.K - 1; ++k) label += (z > tb.edge[k]) ? 1 : 0;
+  return (double)label;
+}
+
 // lanes per row of a likelihood's predictive rule
 __host__ __device__ constexpr int lik_pred_lanes(int lik) {
   return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_GAMMA || lik == HMOGP_LIK_CATEGORICAL) ? 64 : 1;
@@ -877,6 +965,8 @@ __device__ __forceinline__ void lik_eval(double y, double yaux, const double* m,
     lik_beta_wave(y, m, v, lane, etab, o);
   else if (LIK == HMOGP_LIK_STUDENT)
     lik_student_wave(y, m, v, param, lane, etab, o);
+  else if (LIK == HMOGP_LIK_ORDINAL)
+    lik_ordinal(y, yaux, m[0], v[0], param, o);   // y / yaux: the row's lower / upper cut point, param: sigma
   else
     lik_categorical_t<(CATD > 0 ? CATD : 1)>(y, m, v, lane, etab, quirks, o);
   if ((LIK == HMOGP_LIK_GAMMA || LIK == HMOGP_LIK_BETA) && !(quirks & HMOGP_QUIRK_GAMMA_BETA_PI)) {

@@ -1,6 +1,7 @@
 // rowpass.h -- launchers of the row-streaming kernels (rowpass.hip).
 #pragma once
 #include "common.h"
+#include "../../include/hetmogp_hip.h"
 
 #define HMOGP_MAXJ 8  // max latent functions per task (Categorical K <= 9)
 #define HMOGP_MAXQ 8  // max latent GPs
@@ -15,6 +16,7 @@ struct QuadArgs {
   long long off = 0;               // added to the row index of the [Q][ldn] vectors below (0: the pointers are already offset)
   const double* y = nullptr;       // [N]
   const double* yaux = nullptr;    // [N] gammaln(y+1) (Poisson) or nullptr
+  // Ordinal: y / yaux are the row's own LOWER / UPPER cut point (-inf / +inf at the ends) and lik_param is sigma
   const double* p = nullptr;       // [Q][ldn]  K^ a
   const double* c = nullptr;       // [Q][ldn]  rowsum(P~ .* K^)
   const double* pt = nullptr;      // [Q][ldn]  r2-weighted twins (nullptr when no hyper-gradients are wanted)
@@ -138,6 +140,16 @@ struct SmallQuadRed {
   } s[8];
 };
 
+// One registered Ordinal likelihood (hmogp_ordinal_table): K classes, K - 1 cut points, noise scale.  Small enough to
+// travel to the predictive / sampling kernels by value.
+struct OrdinalTable {
+  int K = 0;
+  double sigma = 0.0;
+  double edge[HMOGP_ORDINAL_MAXK - 1];
+};
+// the table behind an Ordinal task's lik_param (engine_linalg.hip; throws HMOGP_E_INVALID for an id that was never handed out)
+const OrdinalTable& ordinal_table(double lik_param);
+
 long long quad_blocks(int lik, long long N);
 // [r5] is there an instantiation of quad_multi_kernel for exactly this set of likelihoods (other than the all-inclusive one, which
 // runs one wave per SIMD)?
@@ -147,6 +159,8 @@ bool quad_multi_specialised(const QuadMulti& m);
 void launch_reduce_rows_multi(const SmallQuadRed& qr, double* dst, hipStream_t s);
 void launch_quad(const QuadArgs& a, hipStream_t s);
 void launch_quad_multi(const QuadMulti& m, hipStream_t s);   // fills blk0 / part0 of the segments; partials laid out segment by segment
+// Ordinal: `param` is the table id in all four building blocks below, and `y` of launch_var_exp / launch_log_predictive is [2][N]:
+// the rows' lower cut points, then their upper ones (ordinal_row_cuts)
 void launch_var_exp(int lik, int J, double param, long long N, const double* y, const double* m, const double* v, double* ve,
                     double* dm, double* dv, hipStream_t s, unsigned quirks = 0x1fu);
 // K[n][m] = var * exp(-r2/2); X rows have stride ldx, Z rows stride ldz (block q of the M x Q*P inducing array)

@@ -392,9 +392,10 @@ __global__ __launch_bounds__(256) void quad_kernel(QuadArgs a) {
 // functions).  One kernel with all fifteen bodies inlined is allocated for the worst of them (256 VGPRs + 32 AGPRs, 380 spilled
 // SGPRs, one wave per SIMD); the sets of the BASELINE configurations get instantiations of their own (C1's
 // {HetGaussian, Bernoulli, Categorical(3)}: see the register table in DESIGN 11e), any other set the all-inclusive one.
-// Student (id 8) takes bit 17, above Categorical's 8 + d (d <= 8), so that no bit of an existing family moves.
+// Student (id 8) takes bit 17, above Categorical's 8 + d (d <= 8), and Ordinal (id 9) bit 18, so that no bit of an existing family moves.
 constexpr unsigned qm_bit(int lik, int dimf) {
-  return lik == HMOGP_LIK_CATEGORICAL ? 1u << (8 + dimf) : (lik == HMOGP_LIK_STUDENT ? 1u << 17 : 1u << lik);
+  return lik == HMOGP_LIK_CATEGORICAL ? 1u << (8 + dimf)
+                                      : (lik == HMOGP_LIK_STUDENT ? 1u << 17 : (lik == HMOGP_LIK_ORDINAL ? 1u << 18 : 1u << lik));
 }
 constexpr unsigned QM_C1 = qm_bit(HMOGP_LIK_HETGAUSSIAN, 0) | qm_bit(HMOGP_LIK_BERNOULLI, 0) | qm_bit(HMOGP_LIK_CATEGORICAL, 2);
 constexpr unsigned QM_H4 = qm_bit(HMOGP_LIK_GAUSSIAN, 0) | qm_bit(HMOGP_LIK_BERNOULLI, 0) | qm_bit(HMOGP_LIK_POISSON, 0) |
@@ -437,7 +438,7 @@ __global__ __launch_bounds__(256) void quad_multi_kernel(QuadMulti m) {
     }                                                          \
   }
   QB(HMOGP_LIK_GAUSSIAN) QB(HMOGP_LIK_BERNOULLI) QB(HMOGP_LIK_HETGAUSSIAN) QB(HMOGP_LIK_POISSON) QB(HMOGP_LIK_EXPONENTIAL)
-  QB(HMOGP_LIK_GAMMA) QB(HMOGP_LIK_BETA) QB(HMOGP_LIK_STUDENT)
+  QB(HMOGP_LIK_GAMMA) QB(HMOGP_LIK_BETA) QB(HMOGP_LIK_STUDENT) QB(HMOGP_LIK_ORDINAL)
   QBC(1) QBC(2) QBC(3) QBC(4) QBC(5) QBC(6) QBC(7) QBC(8)
 #undef QB
 #undef QBC
@@ -722,7 +723,8 @@ __global__ __launch_bounds__(256) void var_exp_kernel(int J, double param, long 
 #pragma unroll
   for (int j = 0; j < HMOGP_MAXJ; ++j) o.gm[j] = o.gv[j] = 0.0;
   const double yy = y[n];
-  lik_eval<LIK, CATD>(yy, (LIK == HMOGP_LIK_POISSON) ? lgamma(yy + 1.0) : 0.0, mu, vv, param, lane, etab[w], quirks, o);
+  const double yaux = (LIK == HMOGP_LIK_POISSON) ? lgamma(yy + 1.0) : ((LIK == HMOGP_LIK_ORDINAL) ? y[N + n] : 0.0);  // Ordinal: y is [2][N]
+  lik_eval<LIK, CATD>(yy, yaux, mu, vv, param, lane, etab[w], quirks, o);
   if (G == 1 || lane == 0) {
     ve[n] = o.ve;
 #pragma unroll
@@ -774,7 +776,7 @@ __global__ __launch_bounds__(256) void log_predictive_kernel(int J, double param
     mu[j] = (j < J) ? m[n * J + j] : 0.0;
     sd[j] = (j < J) ? sqrt(v[n * J + j]) : 0.0;
   }
-  const double yy = y[n], yaux = (LIK == HMOGP_LIK_POISSON) ? lgamma(yy + 1.0) : 0.0;
+  const double yy = y[n], yaux = (LIK == HMOGP_LIK_POISSON) ? lgamma(yy + 1.0) : ((LIK == HMOGP_LIK_ORDINAL) ? y[N + n] : 0.0);
   double mx = -INFINITY, se = 0.0;  // running max / sum of exp(l - max)
   for (int s = lane; s < S; s += 64) {
     double f[HMOGP_MAXJ];
@@ -816,6 +818,26 @@ __global__ __launch_bounds__(256) void sample_kernel(int J, double param, long l
   Y[n] = lik_sample<LIK>(g, f, param);
 }
 
+// ---- Ordinal: closed-form predictive moments and data generation, one lane per row, the table by value ---------
+__global__ __launch_bounds__(256) void ordinal_predictive_kernel(OrdinalTable tb, long long N, const double* __restrict__ m,
+                                                                 const double* __restrict__ v, double* __restrict__ mean,
+                                                                 double* __restrict__ var) {
+  const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  double om, ov;
+  lik_ordinal_predictive(tb, m[n], v[n], om, ov);
+  mean[n] = om;
+  var[n] = ov;
+}
+
+__global__ __launch_bounds__(256) void ordinal_sample_kernel(OrdinalTable tb, long long N, unsigned long long seed,
+                                                             const double* __restrict__ F, double* __restrict__ Y) {
+  const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  RowRng g(seed, n);
+  Y[n] = lik_ordinal_sample(g, tb, F[n]);
+}
+
 }  // namespace
 
 // =============================================================================================== launchers
@@ -834,6 +856,7 @@ void launch_sample(int lik, int J, double param, long long N, unsigned long long
     case HMOGP_LIK_GAMMA: SK(HMOGP_LIK_GAMMA); break;
     case HMOGP_LIK_BETA: SK(HMOGP_LIK_BETA); break;
     case HMOGP_LIK_STUDENT: SK(HMOGP_LIK_STUDENT); break;
+    case HMOGP_LIK_ORDINAL: hipLaunchKernelGGL(ordinal_sample_kernel, grid, dim3(256), 0, s, ordinal_table(param), N, seed, F, Y); break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef SK
@@ -893,6 +916,7 @@ void launch_quad(const QuadArgs& a, hipStream_t s) {
     case HMOGP_LIK_GAMMA: QK(HMOGP_LIK_GAMMA); break;
     case HMOGP_LIK_BETA: QK(HMOGP_LIK_BETA); break;
     case HMOGP_LIK_STUDENT: QK(HMOGP_LIK_STUDENT); break;
+    case HMOGP_LIK_ORDINAL: QK(HMOGP_LIK_ORDINAL); break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef QK
@@ -938,6 +962,7 @@ void launch_quad_multi(const QuadMulti& m_in, hipStream_t s) {
   if ((need & (MASK)) != 0) hipLaunchKernelGGL((quad_multi_kernel<MASK>), dim3(blocks), dim3(256), 0, s, m);
   QMS(QM_LIGHT)
   QMS(qm_bit(HMOGP_LIK_GAMMA, 0)) QMS(qm_bit(HMOGP_LIK_BETA, 0)) QMS(qm_bit(HMOGP_LIK_STUDENT, 0))
+  QMS(qm_bit(HMOGP_LIK_ORDINAL, 0))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 1)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 2)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 3))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 4)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 5)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 6))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 7)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 8))
@@ -972,6 +997,7 @@ void launch_var_exp(int lik, int J, double param, long long N, const double* y, 
     case HMOGP_LIK_GAMMA: VK(HMOGP_LIK_GAMMA); break;
     case HMOGP_LIK_BETA: VK(HMOGP_LIK_BETA); break;
     case HMOGP_LIK_STUDENT: VK(HMOGP_LIK_STUDENT); break;
+    case HMOGP_LIK_ORDINAL: param = ordinal_table(param).sigma; VK(HMOGP_LIK_ORDINAL); break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef VK
@@ -993,6 +1019,7 @@ void launch_predictive(int lik, int J, int Jp, double param, int T, long long N,
     case HMOGP_LIK_GAMMA: PK(HMOGP_LIK_GAMMA); break;
     case HMOGP_LIK_BETA: PK(HMOGP_LIK_BETA); break;
     case HMOGP_LIK_STUDENT: PK(HMOGP_LIK_STUDENT); break;
+    case HMOGP_LIK_ORDINAL: hipLaunchKernelGGL(ordinal_predictive_kernel, grid, dim3(256), 0, s, ordinal_table(param), N, m, v, mean, var); break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef PK
@@ -1011,6 +1038,7 @@ void launch_log_predictive(int lik, int J, double param, long long N, int S, uns
     case HMOGP_LIK_POISSON: LK(HMOGP_LIK_POISSON); break;
     case HMOGP_LIK_EXPONENTIAL: LK(HMOGP_LIK_EXPONENTIAL); break;
     case HMOGP_LIK_STUDENT: LK(HMOGP_LIK_STUDENT); break;
+    case HMOGP_LIK_ORDINAL: param = ordinal_table(param).sigma; LK(HMOGP_LIK_ORDINAL); break;
     default: throw HipError{hipErrorInvalidValue, "the reference defines no log_predictive for this likelihood", __FILE__, __LINE__};
   }
 #undef LK

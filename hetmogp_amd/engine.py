@@ -13,7 +13,7 @@ from ._lib import lib, check
 
 LIK_IDS = dict(Gaussian=_lib.LIK_GAUSSIAN, Bernoulli=_lib.LIK_BERNOULLI, HetGaussian=_lib.LIK_HETGAUSSIAN,
                Categorical=_lib.LIK_CATEGORICAL, Poisson=_lib.LIK_POISSON, Exponential=_lib.LIK_EXPONENTIAL,
-               Gamma=_lib.LIK_GAMMA, Beta=_lib.LIK_BETA, Student=_lib.LIK_STUDENT)
+               Gamma=_lib.LIK_GAMMA, Beta=_lib.LIK_BETA, Student=_lib.LIK_STUDENT, Ordinal=_lib.LIK_ORDINAL)
 
 
 def _f64(a):
@@ -28,7 +28,29 @@ def lik_dim_f(name, **kw):
     """Number of latent parameter functions (the reference's ``get_metadata()[1]``)."""
     if name == "Categorical":
         return int(kw["K"]) - 1
-    return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2)[name]
+    return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1)[name]
+
+
+def ordinal_edges(K=None, bin_edges=None):
+    """The K - 1 cut points of an Ordinal likelihood: `bin_edges` as given, or the unit-spaced ones centred on 0,
+    b_k = k - K/2 (k = 1 .. K-1), when only K is.  Both given must agree.  Their values are checked by the library."""
+    if bin_edges is None:
+        if K is None:
+            raise ValueError("Ordinal needs K or bin_edges")
+        return np.arange(1, int(K), dtype=np.float64) - 0.5 * int(K)
+    edges = np.array(bin_edges, dtype=np.float64).reshape(-1)
+    if K is not None and len(edges) != int(K) - 1:
+        raise ValueError("Ordinal: len(bin_edges) = %d does not agree with K = %d" % (len(edges), int(K)))
+    return edges
+
+
+def ordinal_table(K=None, bin_edges=None, sigma=1.0):
+    """Registers the cut points and sigma of an Ordinal likelihood with the library (`hmogp_ordinal_table`) and returns the id
+    that travels as its `lik_param`.  An identical table gets the same id; an invalid one raises InvalidArgument."""
+    edges = ordinal_edges(K, bin_edges)
+    out = C.c_double(0.0)
+    check(lib.hmogp_ordinal_table(len(edges) + 1, _p(edges), float(sigma), C.byref(out)))
+    return float(out.value)
 
 
 def lik_param(name, **kw):
@@ -39,6 +61,10 @@ def lik_param(name, **kw):
         return float(kw["K"])
     if name == "Student":
         return float(kw.get("deg_free", 5.0))          # nu; the library refuses a nu that is not finite and > 0
+    if name == "Ordinal":
+        if "table_id" in kw:                           # an id from ordinal_table(), passed through as it is
+            return float(kw["table_id"])
+        return ordinal_table(kw.get("K"), kw.get("bin_edges"), kw.get("sigma", 1.0))
     return 0.0
 
 

@@ -126,6 +126,23 @@ class Student(_Lik):
         return {"deg_free": self.deg_free}
 
 
+class Ordinal(_Lik):
+    """Ordered probit (the reference's likelihoods/ordinal.py is a constructor only; the model is DESIGN 9b): one latent function,
+    labels 1..K, p(y = k | f) = Phi((b_k - f) / sigma) - Phi((b_{k-1} - f) / sigma) with fixed cut points b_1 < ... < b_{K-1}
+    (`bin_edges`; K alone: b_k = k - K/2) and fixed sigma.  `gp_link` comes first so that the reference's positional call
+    Ordinal(gp_link) still works.  `predictive` returns the mean and variance of the label, (N, 1) each."""
+    name = "Ordinal"
+
+    def __init__(self, gp_link=None, K=None, bin_edges=None, sigma=1.0):
+        from .engine import ordinal_edges
+        self.bin_edges = ordinal_edges(K, bin_edges)
+        self.K = len(self.bin_edges) + 1
+        self.sigma = float(sigma)
+
+    def kwargs(self):
+        return {"K": self.K, "bin_edges": [float(b) for b in self.bin_edges], "sigma": self.sigma}
+
+
 class Categorical(_Lik):
     name = "Categorical"
 

@@ -4,7 +4,7 @@ task's likelihood; inducing inputs on a grid; lengthscale = c * (inducing spacin
 conditioned at large M.  Used by bench.py, smoke() and the size-property tests."""
 import numpy as np
 
-_DIM_F = dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2)
+_DIM_F = dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1)
 
 
 def _dim_f(name, kw):
@@ -43,6 +43,13 @@ def _sample(rng, name, kw, F):
     if name == "Student":
         nu = kw.get("deg_free", 5.0)
         return F[:, :1] + np.exp(0.5 * F[:, 1:2]) * rng.standard_t(nu, (n, 1))
+    if name == "Ordinal":                      # labels 1..K drawn from the model; F spread so that every class occurs
+        from .engine import ordinal_edges
+        edges = ordinal_edges(kw.get("K"), kw.get("bin_edges"))
+        f = F[:, :1]
+        f = (f - f.mean()) / max(f.std(), 1e-12) * 0.5 * max(edges[-1] - edges[0], 1.0) + 0.5 * (edges[0] + edges[-1])
+        z = f + kw.get("sigma", 1.0) * rng.randn(n, 1)
+        return (1 + (z > edges[None, :]).sum(1, keepdims=True)).astype(float)
     if name == "Categorical":
         K = kw["K"]
         e = np.exp(F[:, :K - 1])

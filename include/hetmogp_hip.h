@@ -43,8 +43,13 @@ enum {
   HMOGP_LIK_EXPONENTIAL = 5, /* exponential.py                                        dim_f = 1   */
   HMOGP_LIK_GAMMA = 6,       /* gamma.py                                              dim_f = 2   */
   HMOGP_LIK_BETA = 7,        /* beta.py                                               dim_f = 2   */
-  HMOGP_LIK_STUDENT = 8      /* student.py      param = deg_free nu (finite, > 0)     dim_f = 2   */
+  HMOGP_LIK_STUDENT = 8,     /* student.py      param = deg_free nu (finite, > 0)     dim_f = 2   */
+  HMOGP_LIK_ORDINAL = 9      /* ordinal.py      param = id from hmogp_ordinal_table   dim_f = 1   */
 };
+
+/* Ordinal (ordered probit): most classes K of one table, and most distinct tables one process can register */
+#define HMOGP_ORDINAL_MAXK 32
+#define HMOGP_ORDINAL_MAXTABLES 4096
 
 /* error codes; the Python facade maps them onto the reference's exception types */
 enum {
@@ -363,6 +368,19 @@ int hmogp_gemm_f64(int32_t device, int32_t transA, int32_t transB, int32_t M, in
 int hmogp_var_exp(int32_t device, int32_t lik_id, double lik_param, int64_t N, const double* y,
                   const double* m, const double* v, double* ve, double* dm, double* dv);
 
+/* Ordinal (ordered probit; the reference's likelihoods/ordinal.py is a constructor only, the model is DESIGN 9b): one latent
+ * function f, labels 1..K, K - 1 cut points b_1 < ... < b_{K-1} (b_0 = -inf, b_K = +inf), fixed noise scale sigma:
+ *   p(y = k | f) = Phi((b_k - f) / sigma) - Phi((b_{k-1} - f) / sigma).
+ * Every entry point carries ONE double per task, so the K numbers of an Ordinal task are registered once: this call checks
+ * them (2 <= K <= HMOGP_ORDINAL_MAXK; edges [K - 1] finite and strictly increasing; sigma finite and > 0), stores an
+ * immutable copy in a process-wide table (thread-safe; an identical table gets the id it already has; at most
+ * HMOGP_ORDINAL_MAXTABLES distinct tables, then HMOGP_E_INVALID) and writes to *lik_param_out the value to pass as
+ * `lik_param` of an HMOGP_LIK_ORDINAL task to hmogp_create / hmogp_var_exp[_ex] / hmogp_predictive / hmogp_log_predictive /
+ * hmogp_sample.  Any other lik_param is HMOGP_E_INVALID there, and so is a label y that is not an integer in 1..K
+ * (hmogp_set_task_data, hmogp_var_exp[_ex], hmogp_log_predictive).  Needs no device.  hmogp_predictive returns the closed-form
+ * moments of the label (mean = sum_k k P_k, var = sum_k k^2 P_k - mean^2; gh_T is ignored).                          */
+int hmogp_ordinal_table(int32_t K, const double* edges, double sigma, double* lik_param_out);
+
 /* The same under a quirk mask (HMOGP_QUIRK_GAMMA_BETA_PI, HMOGP_QUIRK_CATEGORICAL_DM).                            */
 int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t quirks, int64_t N, const double* y,
                      const double* m, const double* v, double* ve, double* dm, double* dv);
@@ -380,7 +398,7 @@ int hmogp_predictive(int32_t device, int32_t lik_id, double lik_param, int32_t g
  * counter-based generator seeded by `seed` (reproducible; a different stream than NumPy's).  The reference then returns
  * (1/S) * sum_n log_pred[n] and HetLikelihood.negative_log_predictive (het_likelihood.py:150-164) negates the sum over
  * tasks -- done by the caller.  Defined for Gaussian, Bernoulli, HetGaussian, Poisson, Exponential, Categorical,
- * Student.                                                                                                     */
+ * Student, Ordinal.                                                                                                       */
 int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64_t N, int32_t num_samples, uint64_t seed,
                          const double* y, const double* m, const double* v, double* log_pred);
 

@@ -325,8 +325,10 @@ def u_algebra(prm, prob, forced_rungs=None):
     return u
 
 
-def local_stats(prm, prob, u, X, Y, batch_scale=None):
+def local_stats(prm, prob, u, X, Y, batch_scale=None, rows_out=None):
     """Row pass over this shard's rows (additive over shards).  Returns the flat statistic bundle.
+    `rows_out` (a list) receives one dict per non-empty task with the per-row quantities behind the bundle: t, K [q], Pt [q], m, v and
+    the SCALED row weights gm, gv (tests/test_rowpass_ref_cpu.py compares them element by element).
 
     prob["strict_qf"] = True restates the engine's HMOGP_CFG_STRICT_QF mode: q(f) and the row side of the gradients through
     triangular solves against Luu (the reference's dpotrs, svmogp_inf.py:214-218) -- since round 6 with only the FORWARD half of
@@ -395,6 +397,8 @@ def local_stats(prm, prob, u, X, Y, batch_scale=None):
         name, kw = prob["specs"][t]
         ve, gm, gv = lo.var_exp_all(name, Y[t], mu, vv, exact=exact, **kw)
         ve, gm, gv = ve * batch_scale[t], gm * batch_scale[t], gv * batch_scale[t]
+        if rows_out is not None:
+            rows_out.append(dict(t=t, K=Khat, Pt=Pt, Kg=Am if strict else Khat, m=mu, v=vv, gm=gm, gv=gv))
         stats[0] += ve.sum()
         stats[1] += float((vv < 0).sum())
         for j, d in enumerate(ds):

@@ -38,8 +38,17 @@ void need_device(int device) {
 }
 
 // y [N] of a building block -> device.  Ordinal: the labels are checked and replaced by the rows' lower, then upper cut points
-// ([2][N], what launch_var_exp / launch_log_predictive read), so that the device code is the engine's.
+// ([2][N], what launch_var_exp / launch_log_predictive read), so that the device code is the engine's.  Dirichlet: y is [N][K]; it is
+// checked and replaced by log y_k as [K][N], the engine's layout.
 void upload_y(int lik_id, double lik_param, const double* y, long long N, DevBuf& dy) {
+  if (lik_id == HMOGP_LIK_DIRICHLET) {
+    const int K = (int)lik_param;
+    std::vector<double> ly((size_t)K * N);
+    dirichlet_log_rows(K, y, N, ly.data());
+    dy.ensure(sizeof(double) * K * N);
+    HIP_TRY(hipMemcpy(dy.p, ly.data(), sizeof(double) * K * N, hipMemcpyHostToDevice));
+    return;
+  }
   if (lik_id != HMOGP_LIK_ORDINAL) {
     dy.ensure(sizeof(double) * N);
     HIP_TRY(hipMemcpy(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice));
@@ -472,7 +481,7 @@ int hmogp_predictive(int32_t device, int32_t lik_id, double lik_param, int32_t g
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);
     check_lik_param(lik_id, lik_param);
-    const int Jp = (lik_id == HMOGP_LIK_CATEGORICAL) ? J : 1;  // dim_p of the reference's get_metadata()
+    const int Jp = (lik_id == HMOGP_LIK_CATEGORICAL || lik_id == HMOGP_LIK_DIRICHLET) ? J : 1;  // dim_p of get_metadata()
     if (gh_T == 0) gh_T = (lik_id == HMOGP_LIK_CATEGORICAL) ? 10 : 20;
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !m || !v || !mean || !var || (gh_T != 10 && gh_T != 20))
       throw EngineError{HMOGP_E_INVALID, "bad arguments"};
@@ -517,12 +526,13 @@ int hmogp_sample(int32_t device, int32_t lik_id, double lik_param, int64_t N, ui
     const int J = lik_dimf(lik_id, lik_param);
     check_lik_param(lik_id, lik_param);
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !F || !Y) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
+    const int Jy = lik_id == HMOGP_LIK_DIRICHLET ? J : 1;   // columns of Y
     DevBuf dF, dY;
-    dF.ensure(sizeof(double) * N * J), dY.ensure(sizeof(double) * N);
+    dF.ensure(sizeof(double) * N * J), dY.ensure(sizeof(double) * N * Jy);
     HIP_TRY(hipMemcpy(dF.p, F, sizeof(double) * N * J, hipMemcpyHostToDevice));
     launch_sample(lik_id, J, lik_param, N, seed, dF.d(), dY.d(), nullptr);
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(Y, dY.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(Y, dY.p, sizeof(double) * N * Jy, hipMemcpyDeviceToHost));
   });
 }
 

@@ -203,15 +203,19 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
     cuts.resize(2 * (size_t)N);               // 1..K is refused before the task's state changes
     ordinal_row_cuts(ordinal_table(k.param), Y, N, cuts.data(), cuts.data() + N);
   }
+  if (k.lik == HMOGP_LIK_DIRICHLET && N > 0) {   // Y is [N, K]; checked, and its logarithm laid out [K][N], before the state changes
+    cuts.resize((size_t)k.dimf * N);
+    dirichlet_log_rows(k.dimf, Y, N, cuts.data());
+  }
   k.N = N;
   began = false;
   staged_key.clear();
   drop_graphs();
   if (N == 0) return;
   k.X.ensure(sizeof(double) * N * P);
-  k.Y.ensure(sizeof(double) * N);
+  k.Y.ensure(sizeof(double) * N * k.dimy());
   HIP_TRY(hipMemcpy(k.X.p, X, sizeof(double) * N * P, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(k.Y.p, Y, sizeof(double) * N, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(k.Y.p, Y, sizeof(double) * N * k.dimy(), hipMemcpyHostToDevice));
   if (k.lik == HMOGP_LIK_POISSON) {  // gammaln(y+1) depends on the data only (poisson.py:33)
     k.Yaux.ensure(sizeof(double) * N);
     launch_gammaln1p(k.Y.d(), k.Yaux.d(), N, st);
@@ -221,6 +225,10 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
     k.Ylo.ensure(sizeof(double) * N), k.Yaux.ensure(sizeof(double) * N);
     HIP_TRY(hipMemcpy(k.Ylo.p, cuts.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(k.Yaux.p, cuts.data() + N, sizeof(double) * N, hipMemcpyHostToDevice));
+  }
+  if (k.lik == HMOGP_LIK_DIRICHLET) {
+    k.Ylo.ensure(sizeof(double) * N * k.dimf);
+    HIP_TRY(hipMemcpy(k.Ylo.p, cuts.data(), sizeof(double) * N * k.dimf, hipMemcpyHostToDevice));
   }
 }
 

@@ -101,17 +101,23 @@ struct Task {
   long long N = 0;
   DevBuf X, Y, Yaux;
   DevBuf Ylo;      // Ordinal: the rows' lower cut points (Yaux holds the upper ones, Y keeps the labels)
+                   // Dirichlet: log y_k as [K][N] (Y keeps the compositions, [N][K])
   int lik = 0, dimf = 1, d0 = 0;
   double param = 0.0;
   double qparam = 0.0;   // what the quadrature kernels get as lik_param: `param`, but sigma for Ordinal (whose param is a table id)
-  const double* quad_y() const { return lik == HMOGP_LIK_ORDINAL ? Ylo.d() : Y.d(); }   // first per-row value of the quadrature
+  const double* quad_y() const { return (lik == HMOGP_LIK_ORDINAL || lik == HMOGP_LIK_DIRICHLET) ? Ylo.d() : Y.d(); }   // first per-row value of the quadrature
+  long long quad_ldy() const { return lik == HMOGP_LIK_DIRICHLET ? N : 0; }   // row stride of quad_y() where a row has K values (QuadArgs::ldy)
+  int dimy() const { return lik == HMOGP_LIK_DIRICHLET ? dimf : 1; }          // columns of the task's Y
   DevBuf offsets;  // device: quad scalar slot -> bundle offset
   int nscal = 0;
 };
 
 int lik_dimf(int lik, double param);
 void check_lik_param(int lik, double param);  // HMOGP_E_INVALID for a parameter the likelihood has no value for (Student: nu;
-                                              // Ordinal: an id hmogp_ordinal_table never returned)
+                                              // Ordinal: an id hmogp_ordinal_table never returned; Dirichlet: K not an integer in
+                                              // 2 .. HMOGP_DIRICHLET_MAXK)
+// Dirichlet: compositions y [N][K] (every y_k finite and > 0, |sum_k y_k - 1| <= 1e-6, else HMOGP_E_INVALID) -> ly [K][N] = log y_k
+void dirichlet_log_rows(int K, const double* y, long long N, double* ly);
 // Ordinal: labels y [N] (integers in 1..K, else HMOGP_E_INVALID) -> the rows' lower / upper cut points (-inf / +inf at the ends)
 void ordinal_row_cuts(const OrdinalTable& tb, const double* y, long long N, double* lo, double* hi);
 // registers (or finds) a table; returns the value to pass as lik_param

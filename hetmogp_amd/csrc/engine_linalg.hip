@@ -20,6 +20,7 @@ int lik_dimf(int lik, double param) {
     case HMOGP_LIK_BETA:
     case HMOGP_LIK_STUDENT: return 2;
     case HMOGP_LIK_CATEGORICAL: return (int)param - 1;
+    case HMOGP_LIK_DIRICHLET: return (param >= 2.0 && param <= (double)HMOGP_DIRICHLET_MAXK) ? (int)param : -1;
     default: return -1;
   }
 }
@@ -28,6 +29,23 @@ void check_lik_param(int lik, double param) {
   if (lik == HMOGP_LIK_STUDENT && !(std::isfinite(param) && param > 0.0))
     throw EngineError{HMOGP_E_INVALID, "Student: deg_free must be finite and > 0"};
   if (lik == HMOGP_LIK_ORDINAL) (void)ordinal_table(param);
+  if (lik == HMOGP_LIK_DIRICHLET && !(param >= 2.0 && param <= (double)HMOGP_DIRICHLET_MAXK && param == std::floor(param)))
+    throw EngineError{HMOGP_E_INVALID, "Dirichlet: K must be an integer in 2 .. HMOGP_DIRICHLET_MAXK"};
+}
+
+// ------------------------------------------------------------------------------------ Dirichlet rows
+void dirichlet_log_rows(int K, const double* y, long long N, double* ly) {
+  for (long long n = 0; n < N; ++n) {
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double yk = y[n * K + k];
+      if (!(std::isfinite(yk) && yk > 0.0))
+        throw EngineError{HMOGP_E_INVALID, "Dirichlet: every y_k must be finite and > 0 (replace zeros before the call)"};
+      s += yk;
+      ly[(long long)k * N + n] = std::log(yk);
+    }
+    if (!(std::fabs(s - 1.0) <= 1e-6)) throw EngineError{HMOGP_E_INVALID, "Dirichlet: a row of Y does not sum to 1 (within 1e-6)"};
+  }
 }
 
 // ------------------------------------------------------------------------------------ Ordinal tables

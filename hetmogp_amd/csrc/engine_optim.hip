@@ -69,6 +69,7 @@ void hmogp_engine::debug_raw(double* o_kmm, double* o_kmn, double* o_kdiag) {
     qa.lik = k.lik, qa.lik_param = k.qparam, qa.dimf = k.dimf, qa.Q = Q, qa.N = sg.n;
     qa.y = k.quad_y() + sg.r0;
     qa.yaux = k.Yaux.p ? k.Yaux.d() + sg.r0 : nullptr;
+    qa.ldy = k.quad_ldy();
     qa.p = vp.d() + sg.off, qa.c = vc.d() + sg.off, qa.pt = vpt.d() + sg.off, qa.ct = vct.d() + sg.off;
     qa.ldn = ldn;
     std::memset(qa.w, 0, sizeof(qa.w)), std::memset(qa.w0, 0, sizeof(qa.w0)), std::memset(qa.kap, 0, sizeof(qa.kap));

@@ -423,6 +423,7 @@ void hmogp_engine::row_pass() {
       qa.lik = k.lik, qa.lik_param = k.qparam, qa.dimf = k.dimf, qa.Q = Q, qa.N = sg.n;
       qa.y = k.quad_y() + sg.r0;
       qa.yaux = k.Yaux.p ? k.Yaux.d() + sg.r0 : nullptr;
+      qa.ldy = k.quad_ldy();
       qa.p = vp.d() + sg.off, qa.c = vc.d() + sg.off;
       const bool row_sl = want_hyper && !col_sl;    // (small-model / strict paths: sl from the row statistics p~, c~)
       qa.pt = row_sl ? vpt.d() + sg.off : nullptr, qa.ct = row_sl ? vct.d() + sg.off : nullptr;
@@ -554,7 +555,7 @@ void hmogp_engine::row_pass() {
         Task& k = tasks[sg.t];
         QuadSeg& g = qm.seg[i];
         g.lik = k.lik, g.dimf = k.dimf, g.d0 = k.d0, g.t = sg.t, g.lik_param = k.qparam, g.N = sg.n, g.off = sg.off;
-        g.y = k.quad_y() + sg.r0, g.yaux = k.Yaux.p ? k.Yaux.d() + sg.r0 : nullptr;
+        g.y = k.quad_y() + sg.r0, g.yaux = k.Yaux.p ? k.Yaux.d() + sg.r0 : nullptr, g.ldy = k.quad_ldy();
         auto& r = qred.s[qred.nseg++];
         r.part = quadpart.d() + part, r.nrows = quad_blocks(k.lik, sg.n), r.nscal = k.nscal, r.off = k.offsets.as<long long>();
         part += r.nrows * k.nscal;

@@ -1,12 +1,13 @@
 // lik_device.h -- device-side variational expectations E_q(f)[log p(y|f)] and their derivatives with respect to
 // the mean / variance of q(f), for the eight likelihoods of /root/reference/likelihoods/*.py (SURVEY.md 8a, rows
 // L1-L8), the heteroscedastic Student-t the reference only stubs (student.py; contract: DESIGN 9) and the Ordinal (ordered
-// probit) likelihood it only stubs as well (ordinal.py; contract: DESIGN 9b; no clip).  Results reproduce the reference's formulas
+// probit) likelihood it only stubs as well (ordinal.py; contract: DESIGN 9b; no clip), and the Dirichlet likelihood, its third stub
+// (dirichlet.py; contract: DESIGN 9d; K log y_k per row).  Results reproduce the reference's formulas
 // including its clips and quirks:
 //   Q1  Gamma / Beta: Gauss-Hermite weights divided by sqrt(pi) twice (gamma.py:110,139-141; beta.py:113,142-144)
 //   Q2  Categorical: d/dm is the constant onehot(y)[d] - 1 (categorical.py:102-113)
 // Lane mapping: closed forms, 1-D quadratures and Gamma (separable in its two functions) use ONE lane per row;
-// Beta (100 nodes), Student (400 nodes) and Categorical (10^(K-1) nodes) use ONE WAVE per row, nodes strided over the
+// Beta (100 nodes), Student (400 nodes), Categorical (10^(K-1) nodes) and Dirichlet (10^K nodes) use ONE WAVE per row, nodes strided over the
 // 64 lanes and reduced with wavefront shuffles.
 #pragma once
 #include "common.h"
@@ -223,7 +224,8 @@ __device__ __forceinline__ void lik_ordinal_predictive(const OrdinalTable& tb, d
 
 // Per-wave LDS scratch of the tensor-rule likelihoods (doubles): Categorical [0,80) exp(f_k(node i)), [80,160) f_k(node i),
 // [160,170) normalised GH weights; Beta [0,80) a_i, psi(a_i), zeta(2,a_i), lgamma(a_i) and the same four for b_j;
-// Student [0,60) r_i = y - f0(node i), f1(node j), s_j = exp(-f1(node j)).
+// Student [0,60) r_i = y - f0(node i), f1(node j), s_j = exp(-f1(node j)); Dirichlet [0,40) a_k(node i), [40,50) weights,
+// [56,64) m_k, v_k (predictive, T = 20: [0,80) a_k(node i), [80,88) m_k, v_k).
 #define HMOGP_ETAB 176
 
 __device__ __forceinline__ double wave_min(double v) {
@@ -301,6 +303,88 @@ __device__ __forceinline__ void lik_beta_wave(double y, const double* m, const d
   o.gm[1] = wave_sum(g1);
   o.gv[0] = 0.5 * wave_sum(h0);
   o.gv[1] = 0.5 * wave_sum(h1);
+}
+
+// ------------------------------------------------------------------------------------------- Dirichlet, 10^K
+// DESIGN 9d (the reference's dirichlet.py is a constructor only).  A row's observation is a composition y on the open simplex; the
+// kernels get ly[k] = log y_k.  K functions, a_k = clip(safe_exp(f_k), 1e-9, 1e9) (Beta's link and clip), A = sum_k a_k:
+//   log p = lgamma(A) - sum_k lgamma(a_k) + sum_k (a_k - 1) ly_k
+//   d/df_k = a_k (psi(A) - psi(a_k) + ly_k)        d2/df_k^2 = d/df_k + a_k^2 (psi'(A) - psi'(a_k))       (the clip is ignored)
+// Under the 10-node-per-dimension tensor rule, weights w/sqrt(pi) once per dimension, W = prod_k w_{i_k}:
+//   ve   = sum_nodes W lgamma(A)  - sum_k sum_i w_i lgamma(a_k(i))      + sum_k (sum_i w_i a_k(i) - 1) ly_k
+//   dm_k = sum_nodes W a_k psi(A) - sum_i w_i a_k(i) psi(a_k(i))        + (sum_i w_i a_k(i)) ly_k
+//   dv_k = 1/2 [ dm_k + sum_nodes W a_k^2 psi'(A) - sum_i w_i a_k(i)^2 psi'(a_k(i)) ]
+// Only the three functions of A couple the dimensions.  The 10 K lanes that fill the wave's table [0, 10 K) a_k(i), [40, 50) weights
+// ([56, 64) m_k, v_k) each add their own one-dimensional term into their running sums, so the reductions at the end deliver both parts at once.
+// A is summed k = 0, 1, .. in this order everywhere (tests/dirichlet_ref.py does the same).
+// The lane that fills table entry (k, i) needs m_k, v_k with a run-time k.  Indexing the register arrays m / v with it parks them (and
+// the LikOut beside them) in scratch, and so does a chain of selects, which the compiler folds back into one indexed load; the wave's
+// own LDS slice takes a run-time index for free, so lane 0 stages the 2 K numbers there: mv[k] = m_k, mv[4 + k] = v_k.
+template <int K>
+__device__ __forceinline__ void dirichlet_stage_mv(const double* m, const double* v, int lane, double* mv) {
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) mv[k] = m[k], mv[4 + k] = v[k];
+  }
+  __builtin_amdgcn_wave_barrier();  // written and read by this wave only (LDS operations of a wave are in order)
+}
+__device__ __forceinline__ double dirichlet_alpha(const double* mv, int k, double x) {
+  return clip(safe_exp(x * sqrt(2.0 * mv[4 + k]) + mv[k]), 1e-9, 1e9);
+}
+
+template <int K>
+__device__ __forceinline__ void lik_dirichlet_wave(const double (&ly)[K], const double* m, const double* v, int lane, double* tab,
+                                                   LikOut& o) {
+  static_assert(K >= 2 && K <= HMOGP_DIRICHLET_MAXK && 10 * HMOGP_DIRICHLET_MAXK + 10 <= HMOGP_ETAB, "Dirichlet table");
+  constexpr int NN = K == 2 ? 100 : (K == 3 ? 1000 : 10000);
+  double* wtab = tab + 40;
+  dirichlet_stage_mv<K>(m, v, lane, tab + 56);
+  double ve = 0.0, g[K], h[K], s1[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) g[k] = h[k] = s1[k] = 0.0;
+  if (lane < 10 * K) {
+    const int k = lane / 10, i = lane - 10 * k;
+    const double a = dirichlet_alpha(tab + 56, k, GH10_X[i]), w = GH10_WN[i];
+    tab[lane] = a;
+    const double wa = w * a, t2 = wa * digamma_pos(a), t3 = wa * a * trigamma_pos(a);
+    ve = -(w * lgamma(a));
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+      if (k == j) s1[j] = wa, g[j] = -t2, h[j] = -t3;
+  }
+  if (lane < 10) wtab[lane] = GH10_WN[lane];
+  __builtin_amdgcn_wave_barrier();  // written and read by this wave only (LDS operations of a wave are in order)
+  for (int n = lane; n < NN; n += 64) {
+    double a[K], W = 1.0;
+    int rem = n;
+#pragma unroll
+    for (int k = K - 1; k >= 0; --k) {
+      const int i = rem % 10;
+      rem /= 10;
+      a[k] = tab[k * 10 + i];
+      W *= wtab[i];
+    }
+    double A = a[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k) A += a[k];
+    const double wp = W * digamma_pos(A), wz = W * trigamma_pos(A);
+    ve = fma(W, lgamma(A), ve);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      g[k] = fma(wp, a[k], g[k]);
+      h[k] = fma(wz * a[k], a[k], h[k]);
+    }
+  }
+  double vs = wave_sum(ve);
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double S1 = wave_sum(s1[k]);
+    vs += (S1 - 1.0) * ly[k];
+    const double gm = wave_sum(g[k]) + S1 * ly[k];
+    o.gm[k] = gm;
+    o.gv[k] = 0.5 * (gm + wave_sum(h[k]));
+  }
+  o.ve = vs;
 }
 
 // ------------------------------------------------------------------------------------------- Student-t, 20 x 20
@@ -747,6 +831,67 @@ __device__ __forceinline__ void lik_predictive(const double* m, const double* v,
   }
 }
 
+// ---- Dirichlet
+// predictive moments of the composition under q(f), T^K tensor rule, one wave per row:
+//   mean_k = E[a_k / A],   var_k = E[a_k (A - a_k) / (A^2 (A + 1))] + E[(a_k / A)^2] - mean_k^2
+template <int K>
+__device__ __forceinline__ void lik_dirichlet_predictive(const double* m, const double* v, int T, int lane, double* tab,
+                                                         double* mean, double* var) {
+  dirichlet_stage_mv<K>(m, v, lane, tab + 80);
+  for (int e = lane; e < K * T; e += 64) {
+    const int k = e / T, i = e - T * k;
+    tab[e] = dirichlet_alpha(tab + 80, k, gh_x(T, i));
+  }
+  __builtin_amdgcn_wave_barrier();
+  int total = 1;
+#pragma unroll
+  for (int k = 0; k < K; ++k) total *= T;
+  double a0[K], a1[K], a2[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) a0[k] = a1[k] = a2[k] = 0.0;
+  for (int n = lane; n < total; n += 64) {
+    double a[K], W = 1.0;
+    int rem = n;
+#pragma unroll
+    for (int k = K - 1; k >= 0; --k) {
+      const int i = rem % T;
+      rem /= T;
+      a[k] = tab[k * T + i];
+      W *= gh_wn(T, i);
+    }
+    double A = a[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k) A += a[k];
+    const double den = A * A * (A + 1.0);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const double p = a[k] / A;
+      a0[k] += W * p;
+      a1[k] += W * (a[k] * (A - a[k]) / den);
+      a2[k] += W * (p * p);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double mu = wave_sum(a0[k]);
+    mean[k] = mu;
+    var[k] = wave_sum(a1[k]) + wave_sum(a2[k]) - mu * mu;
+  }
+}
+
+// the full log p at one sample f of q(f) (Monte-Carlo log predictive)
+template <int K>
+__device__ __forceinline__ double lik_dirichlet_logpdf(const double (&ly)[K], const double* f) {
+  double A = 0.0, r = 0.0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double a = clip(safe_exp(f[k]), 1e-9, 1e9);
+    A += a;
+    r += (a - 1.0) * ly[k] - lgamma(a);
+  }
+  return lgamma(A) + r;
+}
+
 // ============================================================================ Monte-Carlo log predictive
 // log p(y|f) at ONE sample f of q(f), as the reference's `log_predictive` evaluates it (gaussian.py:28-34 -- sigma is
 // ignored, quirk Q6 --, bernoulli.py:31-36, hetgaussian.py:35-39, poisson.py:31-34, exponential.py:28-32,
@@ -936,14 +1081,43 @@ __device__ __forceinline__ double lik_ordinal_sample(RowRng& g, const OrdinalTab
   return (double)label;
 }
 
+// Dirichlet: K Gamma(a_k, 1) variates, normalised.  Where every variate underflows to zero (all a_k tiny: the mass sits on the
+// vertices) the draw is the vertex k with probability a_k / A, the limit of the distribution.
+template <int K>
+__device__ __forceinline__ void lik_dirichlet_sample(RowRng& g, const double* f, double* y) {
+  double a[K], x[K], A = 0.0, s = 0.0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    a[k] = clip(safe_exp(f[k]), 1e-9, 1e9);
+    x[k] = g.gamma(a[k]);
+    A += a[k];
+    s += x[k];
+  }
+  if (s > 0.0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) y[k] = x[k] / s;
+    return;
+  }
+  const double u = g.uniform() * A;
+  double cum = 0.0;
+  bool found = false;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    cum += a[k];
+    const bool hit = !found && (u < cum || k == K - 1);
+    y[k] = hit ? 1.0 : 0.0;
+    found = found || hit;
+  }
+}
+
 // lanes per row of a likelihood's predictive rule
 __host__ __device__ constexpr int lik_pred_lanes(int lik) {
-  return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_GAMMA || lik == HMOGP_LIK_CATEGORICAL) ? 64 : 1;
+  return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_GAMMA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_DIRICHLET) ? 64 : 1;
 }
 
 // lanes per row of a likelihood
 __host__ __device__ constexpr int lik_lanes(int lik) {
-  return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_STUDENT) ? 64 : 1;
+  return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_STUDENT || lik == HMOGP_LIK_DIRICHLET) ? 64 : 1;
 }
 
 // Dispatch.  For 64-lane likelihoods every lane of the wave must call with the same row; the result is valid in

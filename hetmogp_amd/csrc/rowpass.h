@@ -3,7 +3,7 @@
 #include "common.h"
 #include "../../include/hetmogp_hip.h"
 
-#define HMOGP_MAXJ 8  // max latent functions per task (Categorical K <= 9)
+#define HMOGP_MAXJ 8  // max latent functions per task (Categorical K <= 9; Dirichlet K <= 4)
 #define HMOGP_MAXQ 8  // max latent GPs
 // scalar statistics one quad block emits: [0] sum ve, [1] #(v<0), [2+2q] sa_q, [3+2q] sl_q, then J x sgv, then Q x J x swk
 #define HMOGP_MAXSCAL (2 + 2 * HMOGP_MAXQ + HMOGP_MAXJ + HMOGP_MAXQ * HMOGP_MAXJ)
@@ -46,6 +46,9 @@ struct QuadArgs {
   // sa / swk take these explicit-inverse forms instead (K^ a, rowsum(P~ .* K^): the reference's gradient code, :157-161)
   const double* pg = nullptr;          // [Q][ldn] or nullptr (= p)
   const double* cg = nullptr;          // [Q][ldn] or nullptr (= c)
+  // Dirichlet: `y` is row 0 of the task's [K][ldy] array of log y_k, offset to the chunk's first row like every per-row
+  // vector; ldy is the task's own row count, whatever slice of it the chunk is.  No other likelihood reads it.
+  long long ldy = 0;
 };
 
 // strict q(f): the row statistics of the solve-based forms (rowpass.hip: strict_rowstats_kernel)
@@ -104,6 +107,7 @@ struct QuadSeg {
   const double* yaux = nullptr;
   unsigned blk0 = 0;                     // first block of the segment        } filled by launch_quad_multi
   long long part0 = 0;                   // its first word in `partials`      }
+  long long ldy = 0;                     // Dirichlet: row stride of y = log y_k [K][ldy] (QuadArgs::ldy)
 };
 struct QuadMulti {
   int nseg = 0, Q = 1, Df = 0;
@@ -160,7 +164,8 @@ void launch_reduce_rows_multi(const SmallQuadRed& qr, double* dst, hipStream_t s
 void launch_quad(const QuadArgs& a, hipStream_t s);
 void launch_quad_multi(const QuadMulti& m, hipStream_t s);   // fills blk0 / part0 of the segments; partials laid out segment by segment
 // Ordinal: `param` is the table id in all four building blocks below, and `y` of launch_var_exp / launch_log_predictive is [2][N]:
-// the rows' lower cut points, then their upper ones (ordinal_row_cuts)
+// the rows' lower cut points, then their upper ones (ordinal_row_cuts).  Dirichlet: `param` is K, `y` is [K][N]: log y_k (dirichlet_log_rows),
+// launch_predictive writes [N][K] moments and launch_sample [N][K] compositions
 void launch_var_exp(int lik, int J, double param, long long N, const double* y, const double* m, const double* v, double* ve,
                     double* dm, double* dv, hipStream_t s, unsigned quirks = 0x1fu);
 // K[n][m] = var * exp(-r2/2); X rows have stride ldx, Z rows stride ldz (block q of the M x Q*P inducing array)

@@ -266,6 +266,11 @@ __device__ __forceinline__ void quad_body(const QuadArgs& a, unsigned blk, QuadS
     cq[q] = (valid && q < Q) ? a.c[q * a.ldn + nn] : 0.0;
   }
   const double yv = valid ? a.y[n] : 0.0, yauxv = (valid && a.yaux) ? a.yaux[n] : 0.0;
+  double lyv[LIK == HMOGP_LIK_DIRICHLET ? CATD : 1];   // Dirichlet: log y_k of the row, k = 0 .. K - 1 (CATD = K)
+  if constexpr (LIK == HMOGP_LIK_DIRICHLET) {
+#pragma unroll
+    for (int k = 0; k < CATD; ++k) lyv[k] = valid ? a.y[k * a.ldy + n] : 0.0;
+  }
   if (t < HMOGP_MAXQ * HMOGP_MAXJ) {
     const int q = t / HMOGP_MAXJ, j = t % HMOGP_MAXJ;
     const bool in = q < a.Q && j < a.dimf;
@@ -307,7 +312,11 @@ __device__ __forceinline__ void quad_body(const QuadArgs& a, unsigned blk, QuadS
   o.ve = 0.0;
 #pragma unroll
   for (int j = 0; j < HMOGP_MAXJ; ++j) o.gm[j] = o.gv[j] = 0.0;
-  if (valid) lik_eval<LIK, CATD>(yv, yauxv, mu, vv, a.lik_param, lane, etab[w], a.quirks, o);
+  if constexpr (LIK == HMOGP_LIK_DIRICHLET) {
+    if (valid) lik_dirichlet_wave<CATD>(lyv, mu, vv, lane, etab[w], o);
+  } else {
+    if (valid) lik_eval<LIK, CATD>(yv, yauxv, mu, vv, a.lik_param, lane, etab[w], a.quirks, o);
+  }
   if (G == 64 || a.pg) {  // wave-per-row likelihoods: p / c were only needed for q(f); re-read them instead of keeping 2 x MAXQ
                           // doubles alive across the node loop (register pressure = occupancy of the quadrature).
                           // Strict q(f) (a.pg != nullptr): the block scalars sa / swk take the explicit-inverse forms K^ a and
@@ -393,8 +402,10 @@ __global__ __launch_bounds__(256) void quad_kernel(QuadArgs a) {
 // SGPRs, one wave per SIMD); the sets of the BASELINE configurations get instantiations of their own (C1's
 // {HetGaussian, Bernoulli, Categorical(3)}: see the register table in DESIGN 11e), any other set the all-inclusive one.
 // Student (id 8) takes bit 17, above Categorical's 8 + d (d <= 8), and Ordinal (id 9) bit 18, so that no bit of an existing family moves.
+// Dirichlet (id 10) takes bit 19 + (K - 2), K = 2 .. 4: one bit per K, like Categorical, so that each K is an instantiation of its own.
 constexpr unsigned qm_bit(int lik, int dimf) {
   return lik == HMOGP_LIK_CATEGORICAL ? 1u << (8 + dimf)
+         : lik == HMOGP_LIK_DIRICHLET ? 1u << (17 + dimf)
                                       : (lik == HMOGP_LIK_STUDENT ? 1u << 17 : (lik == HMOGP_LIK_ORDINAL ? 1u << 18 : 1u << lik));
 }
 constexpr unsigned QM_C1 = qm_bit(HMOGP_LIK_HETGAUSSIAN, 0) | qm_bit(HMOGP_LIK_BERNOULLI, 0) | qm_bit(HMOGP_LIK_CATEGORICAL, 2);
@@ -412,7 +423,7 @@ __global__ __launch_bounds__(256) void quad_multi_kernel(QuadMulti m) {
   const QuadSeg& g = m.seg[s];
   QuadArgs a;
   a.lik = g.lik, a.lik_param = g.lik_param, a.dimf = g.dimf, a.Q = m.Q, a.N = g.N;
-  a.y = g.y, a.yaux = g.yaux;
+  a.y = g.y, a.yaux = g.yaux, a.ldy = g.ldy;
   a.p = m.p, a.c = m.c, a.pt = m.pt, a.ct = m.ct, a.off = g.off;
   a.ldn = m.ldn;
   a.Wd = m.Wd, a.W0d = m.W0d, a.kapd = m.kapd, a.vard = m.vard, a.scaled = m.scale_base + g.t;
@@ -440,6 +451,15 @@ __global__ __launch_bounds__(256) void quad_multi_kernel(QuadMulti m) {
   QB(HMOGP_LIK_GAUSSIAN) QB(HMOGP_LIK_BERNOULLI) QB(HMOGP_LIK_HETGAUSSIAN) QB(HMOGP_LIK_POISSON) QB(HMOGP_LIK_EXPONENTIAL)
   QB(HMOGP_LIK_GAMMA) QB(HMOGP_LIK_BETA) QB(HMOGP_LIK_STUDENT) QB(HMOGP_LIK_ORDINAL)
   QBC(1) QBC(2) QBC(3) QBC(4) QBC(5) QBC(6) QBC(7) QBC(8)
+#define QBD(K)                                                 \
+  if constexpr ((MASK & qm_bit(HMOGP_LIK_DIRICHLET, K)) != 0) { \
+    if (g.lik == HMOGP_LIK_DIRICHLET && g.dimf == K) {         \
+      quad_body<HMOGP_LIK_DIRICHLET, K, true>(a, blk, sh);     \
+      return;                                                  \
+    }                                                          \
+  }
+  QBD(2) QBD(3) QBD(4)
+#undef QBD
 #undef QB
 #undef QBC
 }
@@ -724,7 +744,14 @@ __global__ __launch_bounds__(256) void var_exp_kernel(int J, double param, long 
   for (int j = 0; j < HMOGP_MAXJ; ++j) o.gm[j] = o.gv[j] = 0.0;
   const double yy = y[n];
   const double yaux = (LIK == HMOGP_LIK_POISSON) ? lgamma(yy + 1.0) : ((LIK == HMOGP_LIK_ORDINAL) ? y[N + n] : 0.0);  // Ordinal: y is [2][N]
-  lik_eval<LIK, CATD>(yy, yaux, mu, vv, param, lane, etab[w], quirks, o);
+  if constexpr (LIK == HMOGP_LIK_DIRICHLET) {  // y is [K][N]: log y_k (CATD = K)
+    double ly[CATD > 0 ? CATD : 1];
+#pragma unroll
+    for (int k = 0; k < CATD; ++k) ly[k] = y[k * N + n];
+    lik_dirichlet_wave<CATD>(ly, mu, vv, lane, etab[w], o);
+  } else {
+    lik_eval<LIK, CATD>(yy, yaux, mu, vv, param, lane, etab[w], quirks, o);
+  }
   if (G == 1 || lane == 0) {
     ve[n] = o.ve;
 #pragma unroll
@@ -838,7 +865,93 @@ __global__ __launch_bounds__(256) void ordinal_sample_kernel(OrdinalTable tb, lo
   Y[n] = lik_ordinal_sample(g, tb, F[n]);
 }
 
+// ---- Dirichlet: kernels of their own per K (the row carries K values where the generic kernels carry one) ---------
+template <int K>
+__global__ __launch_bounds__(256) void dirichlet_predictive_kernel(int T, long long N, const double* __restrict__ m,
+                                                                   const double* __restrict__ v, double* __restrict__ mean,
+                                                                   double* __restrict__ var) {
+  __shared__ double etab[4][HMOGP_ETAB];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long n = (long long)blockIdx.x * 4 + w;
+  if (n >= N) return;
+  double mu[K], vv[K], om[K], ov[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) mu[k] = m[n * K + k], vv[k] = v[n * K + k];
+  lik_dirichlet_predictive<K>(mu, vv, T, lane, etab[w], om, ov);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) mean[n * K + k] = om[k], var[n * K + k] = ov[k];
+  }
+}
+
+// y: [K][N] log y_k; samples strided over the lanes as in log_predictive_kernel (same generator, same combination)
+template <int K>
+__global__ __launch_bounds__(256) void dirichlet_log_predictive_kernel(long long N, int S, unsigned long long seed,
+                                                                       const double* __restrict__ y, const double* __restrict__ m,
+                                                                       const double* __restrict__ v, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  double mu[4], sd[4], ly[K];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    mu[j] = (j < K) ? m[n * K + j] : 0.0;
+    sd[j] = (j < K) ? sqrt(v[n * K + j]) : 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) ly[k] = y[k * N + n];
+  double mx = -INFINITY, se = 0.0;
+  for (int s = lane; s < S; s += 64) {
+    double f[4];
+#pragma unroll
+    for (int j = 0; j < 4; j += 2) {
+      double z0 = 0.0, z1 = 0.0;
+      if (j < K) normal_pair(seed, n, s, j >> 1, z0, z1);
+      f[j] = mu[j] + sd[j] * z0;
+      f[j + 1] = mu[j + 1] + sd[j + 1] * z1;
+    }
+    const double l = lik_dirichlet_logpdf<K>(ly, f);
+    if (l > mx) {
+      se = se * exp(mx - l) + 1.0;
+      mx = l;
+    } else {
+      se += exp(l - mx);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double omx = __shfl_xor(mx, o, 64), ose = __shfl_xor(se, o, 64);
+    const double nm = fmax(mx, omx);
+    se = (mx == -INFINITY ? 0.0 : se * exp(mx - nm)) + (omx == -INFINITY ? 0.0 : ose * exp(omx - nm));
+    mx = nm;
+  }
+  if (lane == 0) out[n] = -log((double)S) + mx + log(se);
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void dirichlet_sample_kernel(long long N, unsigned long long seed, const double* __restrict__ F,
+                                                               double* __restrict__ Y) {
+  const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  double f[K], yv[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) f[k] = F[n * K + k];
+  RowRng g(seed, n);
+  lik_dirichlet_sample<K>(g, f, yv);
+#pragma unroll
+  for (int k = 0; k < K; ++k) Y[n * K + k] = yv[k];
+}
+
 }  // namespace
+
+// launches KERNEL<K> for the K of a Dirichlet task (already checked by check_lik_param; anything else is a caller's bug)
+#define DISPATCH_DIRK(K_, ...)                                                                                   \
+  switch (K_) {                                                                                                  \
+    case 2: { constexpr int DK = 2; __VA_ARGS__; } break;                                                        \
+    case 3: { constexpr int DK = 3; __VA_ARGS__; } break;                                                        \
+    case 4: { constexpr int DK = 4; __VA_ARGS__; } break;                                                        \
+    default: throw HipError{hipErrorInvalidValue, "Dirichlet needs 2 <= K <= HMOGP_DIRICHLET_MAXK", __FILE__, __LINE__}; \
+  }
 
 // =============================================================================================== launchers
 void launch_sample(int lik, int J, double param, long long N, unsigned long long seed, const double* F, double* Y,
@@ -857,6 +970,9 @@ void launch_sample(int lik, int J, double param, long long N, unsigned long long
     case HMOGP_LIK_BETA: SK(HMOGP_LIK_BETA); break;
     case HMOGP_LIK_STUDENT: SK(HMOGP_LIK_STUDENT); break;
     case HMOGP_LIK_ORDINAL: hipLaunchKernelGGL(ordinal_sample_kernel, grid, dim3(256), 0, s, ordinal_table(param), N, seed, F, Y); break;
+    case HMOGP_LIK_DIRICHLET:
+      DISPATCH_DIRK(J, hipLaunchKernelGGL((dirichlet_sample_kernel<DK>), grid, dim3(256), 0, s, N, seed, F, Y));
+      break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef SK
@@ -917,6 +1033,9 @@ void launch_quad(const QuadArgs& a, hipStream_t s) {
     case HMOGP_LIK_BETA: QK(HMOGP_LIK_BETA); break;
     case HMOGP_LIK_STUDENT: QK(HMOGP_LIK_STUDENT); break;
     case HMOGP_LIK_ORDINAL: QK(HMOGP_LIK_ORDINAL); break;
+    case HMOGP_LIK_DIRICHLET:
+      DISPATCH_DIRK(a.dimf, hipLaunchKernelGGL((quad_kernel<HMOGP_LIK_DIRICHLET, DK>), grid, dim3(256), 0, s, a));
+      break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef QK
@@ -939,6 +1058,8 @@ void launch_quad_multi(const QuadMulti& m_in, hipStream_t s) {
     QuadSeg& g = m.seg[i];
     if (g.lik == HMOGP_LIK_CATEGORICAL && (g.dimf < 1 || g.dimf > 8))
       throw HipError{hipErrorInvalidValue, "Categorical needs 2 <= K <= 9", __FILE__, __LINE__};
+    if (g.lik == HMOGP_LIK_DIRICHLET && (g.dimf < 2 || g.dimf > HMOGP_DIRICHLET_MAXK))
+      throw HipError{hipErrorInvalidValue, "Dirichlet needs 2 <= K <= HMOGP_DIRICHLET_MAXK", __FILE__, __LINE__};
     g.blk0 = blocks, g.part0 = part;
     const long long nb = quad_blocks(g.lik, g.N);
     blocks += (unsigned)nb;
@@ -963,6 +1084,7 @@ void launch_quad_multi(const QuadMulti& m_in, hipStream_t s) {
   QMS(QM_LIGHT)
   QMS(qm_bit(HMOGP_LIK_GAMMA, 0)) QMS(qm_bit(HMOGP_LIK_BETA, 0)) QMS(qm_bit(HMOGP_LIK_STUDENT, 0))
   QMS(qm_bit(HMOGP_LIK_ORDINAL, 0))
+  QMS(qm_bit(HMOGP_LIK_DIRICHLET, 2)) QMS(qm_bit(HMOGP_LIK_DIRICHLET, 3)) QMS(qm_bit(HMOGP_LIK_DIRICHLET, 4))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 1)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 2)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 3))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 4)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 5)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 6))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 7)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 8))
@@ -998,6 +1120,10 @@ void launch_var_exp(int lik, int J, double param, long long N, const double* y, 
     case HMOGP_LIK_BETA: VK(HMOGP_LIK_BETA); break;
     case HMOGP_LIK_STUDENT: VK(HMOGP_LIK_STUDENT); break;
     case HMOGP_LIK_ORDINAL: param = ordinal_table(param).sigma; VK(HMOGP_LIK_ORDINAL); break;
+    case HMOGP_LIK_DIRICHLET:
+      DISPATCH_DIRK(J, hipLaunchKernelGGL((var_exp_kernel<HMOGP_LIK_DIRICHLET, DK>), grid, dim3(256), 0, s, J, param, N, y, m, v, ve,
+                                          dm, dv, quirks));
+      break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef VK
@@ -1020,6 +1146,9 @@ void launch_predictive(int lik, int J, int Jp, double param, int T, long long N,
     case HMOGP_LIK_BETA: PK(HMOGP_LIK_BETA); break;
     case HMOGP_LIK_STUDENT: PK(HMOGP_LIK_STUDENT); break;
     case HMOGP_LIK_ORDINAL: hipLaunchKernelGGL(ordinal_predictive_kernel, grid, dim3(256), 0, s, ordinal_table(param), N, m, v, mean, var); break;
+    case HMOGP_LIK_DIRICHLET:   // (64 lanes per row: the grid above is one block per 4 rows)
+      DISPATCH_DIRK(J, hipLaunchKernelGGL((dirichlet_predictive_kernel<DK>), grid, dim3(256), 0, s, T, N, m, v, mean, var));
+      break;
     default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
   }
 #undef PK
@@ -1039,6 +1168,9 @@ void launch_log_predictive(int lik, int J, double param, long long N, int S, uns
     case HMOGP_LIK_EXPONENTIAL: LK(HMOGP_LIK_EXPONENTIAL); break;
     case HMOGP_LIK_STUDENT: LK(HMOGP_LIK_STUDENT); break;
     case HMOGP_LIK_ORDINAL: param = ordinal_table(param).sigma; LK(HMOGP_LIK_ORDINAL); break;
+    case HMOGP_LIK_DIRICHLET:
+      DISPATCH_DIRK(J, hipLaunchKernelGGL((dirichlet_log_predictive_kernel<DK>), grid, dim3(256), 0, s, N, S, seed, y, m, v, out));
+      break;
     default: throw HipError{hipErrorInvalidValue, "the reference defines no log_predictive for this likelihood", __FILE__, __LINE__};
   }
 #undef LK

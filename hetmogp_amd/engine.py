@@ -13,7 +13,8 @@ from ._lib import lib, check
 
 LIK_IDS = dict(Gaussian=_lib.LIK_GAUSSIAN, Bernoulli=_lib.LIK_BERNOULLI, HetGaussian=_lib.LIK_HETGAUSSIAN,
                Categorical=_lib.LIK_CATEGORICAL, Poisson=_lib.LIK_POISSON, Exponential=_lib.LIK_EXPONENTIAL,
-               Gamma=_lib.LIK_GAMMA, Beta=_lib.LIK_BETA, Student=_lib.LIK_STUDENT, Ordinal=_lib.LIK_ORDINAL)
+               Gamma=_lib.LIK_GAMMA, Beta=_lib.LIK_BETA, Student=_lib.LIK_STUDENT, Ordinal=_lib.LIK_ORDINAL,
+               Dirichlet=_lib.LIK_DIRICHLET)
 
 
 def _f64(a):
@@ -28,7 +29,20 @@ def lik_dim_f(name, **kw):
     """Number of latent parameter functions (the reference's ``get_metadata()[1]``)."""
     if name == "Categorical":
         return int(kw["K"]) - 1
+    if name == "Dirichlet":
+        return int(kw["K"])
     return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1)[name]
+
+
+def lik_dim_y(name, **kw):
+    """Columns of a task's Y (the reference's ``get_metadata()[0]``): 1, but K for a Dirichlet task."""
+    return int(kw["K"]) if name == "Dirichlet" else 1
+
+
+def _y_rows(name, y, **kw):
+    """y of one task as the library reads it: (N,), or (N, K) row-major for a Dirichlet task."""
+    dy = lik_dim_y(name, **kw)
+    return _f64(y).reshape(-1) if dy == 1 else _f64(y).reshape(-1, dy)
 
 
 def ordinal_edges(K=None, bin_edges=None):
@@ -57,7 +71,7 @@ def lik_param(name, **kw):
     if name == "Gaussian":
         s = kw.get("sigma")
         return 0.5 if s is None else float(s)          # gaussian.py:21-24
-    if name == "Categorical":
+    if name in ("Categorical", "Dirichlet"):           # (Dirichlet: the library refuses a K outside 2 .. DIRICHLET_MAXK)
         return float(kw["K"])
     if name == "Student":
         return float(kw.get("deg_free", 5.0))          # nu; the library refuses a nu that is not finite and > 0
@@ -153,7 +167,7 @@ class Engine(object):
 
     # ------------------------------------------------------------------------------------------ data
     def set_task_data(self, t, X, Y):
-        X, Y = _f64(X).reshape(-1, self.P), _f64(Y).reshape(-1)
+        X, Y = _f64(X).reshape(-1, self.P), _y_rows(self.specs[t][0], Y, **self.specs[t][1])
         if X.shape[0] != Y.shape[0]:
             raise ValueError("X and Y of task %d have different lengths" % t)
         check(lib.hmogp_set_task_data(self._h, t, _p(X), _p(Y), X.shape[0]), self._h)
@@ -509,7 +523,7 @@ def gemm(A, B, transA=False, transB=False, alpha=1.0, beta=0.0, C0=None, device=
 
 def var_exp(name, y, m, v, device=None, quirks="reference", **kw):
     device = _resolve_device(device)
-    y, m, v = _f64(y).reshape(-1), _f64(m), _f64(v)
+    y, m, v = _y_rows(name, y, **kw), _f64(m), _f64(v)
     J = lik_dim_f(name, **kw)
     m, v = m.reshape(-1, J), v.reshape(-1, J)
     ve, dm, dv = np.zeros(y.shape[0]), np.zeros_like(m), np.zeros_like(v)
@@ -524,7 +538,7 @@ def predictive(name, m, v, gh_T=0, device=None, **kw):
     m, v = _f64(m), _f64(v)
     J = lik_dim_f(name, **kw)
     m, v = m.reshape(-1, J), v.reshape(-1, J)
-    Jp = J if name == "Categorical" else 1
+    Jp = J if name in ("Categorical", "Dirichlet") else 1
     mean, var = np.zeros((m.shape[0], Jp)), np.zeros((m.shape[0], Jp))
     check(lib.hmogp_predictive(device, LIK_IDS[name], lik_param(name, **kw), int(gh_T), m.shape[0], _p(m), _p(v), _p(mean),
                                _p(var)))
@@ -534,7 +548,7 @@ def predictive(name, m, v, gh_T=0, device=None, **kw):
 def log_predictive_rows(name, y, m, v, num_samples=1000, seed=0, device=None, **kw):
     """Per-row Monte-Carlo log predictive density: -log S + logsumexp_s log p(y_n | f_s), f_s ~ N(m_n, diag v_n)."""
     device = _resolve_device(device)
-    y, m, v = _f64(y).reshape(-1), _f64(m), _f64(v)
+    y, m, v = _y_rows(name, y, **kw), _f64(m), _f64(v)
     J = lik_dim_f(name, **kw)
     m, v = m.reshape(-1, J), v.reshape(-1, J)
     out = np.zeros(y.shape[0])
@@ -544,10 +558,11 @@ def log_predictive_rows(name, y, m, v, num_samples=1000, seed=0, device=None, **
 
 
 def sample(name, F, seed=0, device=None, **kw):
-    """One draw y ~ p(y | F[n]) per row on the device (the reference's `<likelihood>.samples`): returns (N, 1)."""
+    """One draw y ~ p(y | F[n]) per row on the device (the reference's `<likelihood>.samples`): returns (N, 1); (N, K) for
+    Dirichlet."""
     device = _resolve_device(device)
     J = lik_dim_f(name, **kw)
     F = _f64(F).reshape(-1, J)
-    Y = np.zeros(F.shape[0])
+    Y = np.zeros((F.shape[0], lik_dim_y(name, **kw)))
     check(lib.hmogp_sample(device, LIK_IDS[name], lik_param(name, **kw), F.shape[0], int(seed) & (2 ** 64 - 1), _p(F), _p(Y)))
-    return Y[:, None]
+    return Y

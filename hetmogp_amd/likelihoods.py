@@ -42,7 +42,7 @@ class _Lik(object):
         return predictive(self.name, m, v, **self.kwargs())
 
     def samples(self, F, num_samples=1, Y_metadata=None, seed=None):
-        """One draw y ~ p(y | F[n]) per row, (N, 1) -- the reference's `samples` (e.g. gaussian.py:36-39, gamma.py:43-50,
+        """One draw y ~ p(y | F[n]) per row, (N, 1); (N, K) for Dirichlet -- the reference's `samples` (e.g. gaussian.py:36-39, gamma.py:43-50,
         categorical.py:65-75: same link functions and clips, labels 1..K), generated on the device (`hmogp_sample`).
         The reference draws from NumPy's global generator; here the device generator is keyed by `seed`, which is itself
         drawn from NumPy's global generator when not given -- so `np.random.seed(k)` still makes a run reproducible, but
@@ -141,6 +141,32 @@ class Ordinal(_Lik):
 
     def kwargs(self):
         return {"K": self.K, "bin_edges": [float(b) for b in self.bin_edges], "sigma": self.sigma}
+
+
+class Dirichlet(_Lik):
+    """Compositions (the reference's likelihoods/dirichlet.py is a constructor only; the model is DESIGN 9d): a row of Y is
+    y = (y_1 .. y_K) on the open simplex, K latent functions, alpha_k = clip(exp(f_k), 1e-9, 1e9) -- the K-part generalisation of
+    Beta.  `K` comes first, like Categorical; 2 <= K <= 4.  Y is (N, K): every y_k must be finite and > 0 and every row must sum to
+    1 within 1e-6, so zeros have to be replaced by the caller (as is usual for compositions) before the data is handed over.
+    `predictive` returns the mean and variance of every part, (N, K) each; `samples` returns (N, K).  Where every alpha_k sits at
+    the lower clip all K Gamma variates underflow and `samples` returns a vertex of the simplex (parts that are exactly 0 and 1, the
+    limit of the distribution): such draws have to be moved off the boundary like any other zeros before they are used as data.
+    The link is fixed (`gp_link` is accepted for the reference's signature and not used)."""
+    name = "Dirichlet"
+
+    def __init__(self, K, gp_link=None):
+        if int(K) != K or not 2 <= int(K) <= 4:
+            raise ValueError("Dirichlet: K must be an integer in 2 .. 4, got %r" % (K,))
+        self.K = int(K)
+
+    def kwargs(self):
+        return {"K": self.K}
+
+    def get_metadata(self):
+        return self.K, self.K, self.K
+
+    def ismulti(self):
+        return True
 
 
 class Categorical(_Lik):

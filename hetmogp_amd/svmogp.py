@@ -319,7 +319,8 @@ class SVMOGP(object):
             _, self.kappa_list = util.random_W_kappas(self.num_latent_funcs, self.num_output_funcs, rank=1)
 
         self.Xmulti_all = [np.ascontiguousarray(x, dtype=float).reshape(x.shape[0], -1) for x in X]
-        self.Ymulti_all = [np.ascontiguousarray(y, dtype=float).reshape(-1, 1) for y in Y]
+        self._dim_y = [lik.get_metadata()[0] for lik in likelihood.likelihoods_list]   # columns of a task's Y (1; Dirichlet: K)
+        self.Ymulti_all = [np.ascontiguousarray(y, dtype=float).reshape(-1, dy) for y, dy in zip(Y, self._dim_y)]
         T = len(self.Ymulti_all)
         self.Xdim = Z.shape[1]
         if isinstance(strict_qf, str) and strict_qf != "auto":
@@ -536,7 +537,7 @@ class SVMOGP(object):
             self._rows = list(self._last_batch[2])
         else:
             Xc = [np.ascontiguousarray(x, dtype=float).reshape(x.shape[0], -1) for x in X]
-            Yc = [np.ascontiguousarray(y, dtype=float).reshape(-1, 1) for y in Y]
+            Yc = [np.ascontiguousarray(y, dtype=float).reshape(-1, dy) for y, dy in zip(Y, self._dim_y)]
             self._engine.set_data(Xc, Yc)
             self._engine_has_full = False
             self._rows = [(0, x.shape[0]) for x in Xc]

@@ -8,7 +8,7 @@ _DIM_F = dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, 
 
 
 def _dim_f(name, kw):
-    return kw["K"] - 1 if name == "Categorical" else _DIM_F[name]
+    return kw["K"] - 1 if name == "Categorical" else (kw["K"] if name == "Dirichlet" else _DIM_F[name])
 
 
 def _true_u(rng, x, Q):
@@ -50,6 +50,9 @@ def _sample(rng, name, kw, F):
         f = (f - f.mean()) / max(f.std(), 1e-12) * 0.5 * max(edges[-1] - edges[0], 1.0) + 0.5 * (edges[0] + edges[-1])
         z = f + kw.get("sigma", 1.0) * rng.randn(n, 1)
         return (1 + (z > edges[None, :]).sum(1, keepdims=True)).astype(float)
+    if name == "Dirichlet":                    # compositions drawn from the model, kept off the boundary and renormalised
+        g = np.maximum(rng.gamma(np.exp(np.clip(F[:, :kw["K"]], -2, 2))), 1e-6)
+        return g / g.sum(1, keepdims=True)
     if name == "Categorical":
         K = kw["K"]
         e = np.exp(F[:, :K - 1])

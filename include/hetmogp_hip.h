@@ -44,12 +44,23 @@ enum {
   HMOGP_LIK_GAMMA = 6,       /* gamma.py                                              dim_f = 2   */
   HMOGP_LIK_BETA = 7,        /* beta.py                                               dim_f = 2   */
   HMOGP_LIK_STUDENT = 8,     /* student.py      param = deg_free nu (finite, > 0)     dim_f = 2   */
-  HMOGP_LIK_ORDINAL = 9      /* ordinal.py      param = id from hmogp_ordinal_table   dim_f = 1   */
+  HMOGP_LIK_ORDINAL = 9,     /* ordinal.py      param = id from hmogp_ordinal_table   dim_f = 1   */
+  HMOGP_LIK_DIRICHLET = 10   /* dirichlet.py    param = K (2 .. HMOGP_DIRICHLET_MAXK)  dim_f = K, Y is [N, K] */
 };
 
 /* Ordinal (ordered probit): most classes K of one table, and most distinct tables one process can register */
 #define HMOGP_ORDINAL_MAXK 32
 #define HMOGP_ORDINAL_MAXTABLES 4096
+
+/* Dirichlet (the reference's likelihoods/dirichlet.py is a constructor only): a row's observation is a composition
+ * y = (y_1 .. y_K) on the open simplex, K latent functions, alpha_k = clip(exp(f_k), 1e-9, 1e9), A = sum_k alpha_k:
+ *   log p(y | f) = lgamma(A) - sum_k lgamma(alpha_k) + sum_k (alpha_k - 1) log y_k.
+ * It is the one family whose Y has more than one column: wherever another family passes y [N], a Dirichlet task passes
+ * Y [N, K] row-major (hmogp_set_task_data, hmogp_var_exp[_ex], hmogp_log_predictive), and hmogp_sample writes [N, K].  A y_k that
+ * is not finite, is <= 0, or a row with |sum_k y_k - 1| > 1e-6 is HMOGP_E_INVALID (zeros must be replaced by the caller), and so
+ * is a lik_param that is not an integer in 2 .. HMOGP_DIRICHLET_MAXK, in hmogp_create and in every building block.  The bound on
+ * K is the 10^K nodes of the tensor rule and the per-wave table of the quadrature kernels. */
+#define HMOGP_DIRICHLET_MAXK 4
 
 /* error codes; the Python facade maps them onto the reference's exception types */
 enum {
@@ -199,7 +210,8 @@ void hmogp_destroy(hmogp_handle h);
 const char* hmogp_last_error(hmogp_handle h); /* h may be NULL: error of the last failed hmogp_create    */
 int hmogp_abi_version(void);
 
-/* Upload (replace) the full data of task t: X [N, P], Y [N] (Xmulti_all[t], Ymulti_all[t]).            */
+/* Upload (replace) the full data of task t: X [N, P], Y [N] (Xmulti_all[t], Ymulti_all[t]).  A Dirichlet task's Y is [N, K]
+ * row-major; it is checked (see HMOGP_DIRICHLET_MAXK) before the task's state changes.                                  */
 int hmogp_set_task_data(hmogp_handle h, int32_t t, const double* X, const double* Y, int64_t N);
 
 /* ---- the hot path ----------------------------------------------------------------------------------- */
@@ -362,7 +374,7 @@ int hmogp_potrs_rows(int32_t device, const double* L, int32_t M, const double* B
 int hmogp_gemm_f64(int32_t device, int32_t transA, int32_t transB, int32_t M, int32_t N, int32_t K,
                    double alpha, const double* A, int32_t lda, const double* B, int32_t ldb, double beta,
                    double* C, int32_t ldc);
-/* Variational expectations of one likelihood: y [N], m,v [N, dim_f] -> ve [N], dm, dv [N, dim_f].
+/* Variational expectations of one likelihood: y [N] (Dirichlet: [N, K]), m,v [N, dim_f] -> ve [N], dm, dv [N, dim_f].
  * Here and in hmogp_predictive / hmogp_log_predictive / hmogp_sample / hmogp_create a Student deg_free that is not
  * finite and > 0 is HMOGP_E_INVALID.                                                                      */
 int hmogp_var_exp(int32_t device, int32_t lik_id, double lik_param, int64_t N, const double* y,
@@ -387,7 +399,7 @@ int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t 
 
 /* Predictive mean / variance of y under q(f) = N(m, diag v): the reference's `<likelihood>.predictive(m, v)`
  * (e.g. bernoulli.py:113-128, gamma.py:196-238, categorical.py:224-269), consumed by HetLikelihood.predictive
- * (het_likelihood.py:133-148).  m, v [N, dim_f] -> mean, var [N, dim_p] (dim_p = K-1 for Categorical, else 1).
+ * (het_likelihood.py:133-148).  m, v [N, dim_f] -> mean, var [N, dim_p] (dim_p = K-1 for Categorical, K for Dirichlet, else 1).
  * gh_T: Gauss-Hermite order, 20 (fresh reference instance), 10 (instance whose var_exp ran first: GPy caches the
  * first rule), 0 = the reference's default for a fresh instance.                                              */
 int hmogp_predictive(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, const double* m,
@@ -398,14 +410,15 @@ int hmogp_predictive(int32_t device, int32_t lik_id, double lik_param, int32_t g
  * counter-based generator seeded by `seed` (reproducible; a different stream than NumPy's).  The reference then returns
  * (1/S) * sum_n log_pred[n] and HetLikelihood.negative_log_predictive (het_likelihood.py:150-164) negates the sum over
  * tasks -- done by the caller.  Defined for Gaussian, Bernoulli, HetGaussian, Poisson, Exponential, Categorical,
- * Student, Ordinal.                                                                                                       */
+ * Student, Ordinal, Dirichlet (y [N, K]).                                                                                 */
 int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64_t N, int32_t num_samples, uint64_t seed,
                          const double* y, const double* m, const double* v, double* log_pred);
 
 /* Data generation on the device: one draw Y[n] ~ p(y | F[n, :]) per row with the link functions and clips of the
  * reference's `<likelihood>.samples` (het_likelihood.py:72-83 -> e.g. gamma.py:43-50, categorical.py:65-75; labels of
  * Categorical are 1..K).  Counter-based generator keyed by (seed, row): reproducible, but a different stream than
- * NumPy's -- only the distribution is comparable with the reference.                                             */
+ * NumPy's -- only the distribution is comparable with the reference.  Y is [N]; Dirichlet writes [N, K] (K Gamma(alpha_k, 1)
+ * variates, normalised).                                                                                        */
 int hmogp_sample(int32_t device, int32_t lik_id, double lik_param, int64_t N, uint64_t seed, const double* F /* [N, dim_f] */,
                  double* Y /* [N] */);
 

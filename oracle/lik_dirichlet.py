@@ -160,20 +160,3 @@ def log_predictive_rows(y, m, v, num_samples, rng, K):
     p = np.exp(l - mx)
     est = mx[:, 0] + np.log(p.mean(1))
     return est, p.std(1, ddof=1) / np.sqrt(num_samples) / p.mean(1)
-
-
-def install(monkeypatch):
-    """Dispatch "Dirichlet" in the oracle's likelihood module to this file; every other family keeps the original."""
-    from oracle import likelihoods_oracle as lo
-    orig_var_exp_all, orig_dim_f = lo.var_exp_all, lo.dim_f
-
-    def var_exp_all(name, y, m, v, exact=False, **kw):
-        if name == "Dirichlet":
-            return var_exp(y, m, v, **kw)
-        return orig_var_exp_all(name, y, m, v, exact=exact, **kw)
-
-    def dim_f(name, K=None):
-        return int(K) if name == "Dirichlet" else orig_dim_f(name, K)
-
-    monkeypatch.setattr(lo, "var_exp_all", var_exp_all)
-    monkeypatch.setattr(lo, "dim_f", dim_f)

@@ -1,7 +1,5 @@
-"""NumPy restatement of the heteroscedastic Student-t likelihood for the tests: the reference ships only a
-constructor (likelihoods/student.py), so the oracle has no Student of its own.  `install(monkeypatch)` routes
-`oracle.likelihoods_oracle.var_exp_all` / `dim_f` -- which `oracle.svmogp_oracle` looks up through the module at call time --
-to this file for "Student" and to the originals for every other family, so the unchanged whole-model oracle covers it.
+"""NumPy restatement of the heteroscedastic Student-t likelihood: the reference ships only a constructor
+(likelihoods/student.py), so this file restates the project's own contract.  `oracle.likelihoods_oracle` dispatches "Student" here.
 
 Model: f0 = location (identity link), f1 = log of the squared scale, nu = deg_free fixed.  With r = y - f0,
 s = exp(min(-f1, LIM_VAL)), u = r^2 s / nu and C = lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2:
@@ -55,20 +53,3 @@ def predictive(m, v, deg_free=5.0):
     mean = m[:, :1] if nu > 1.0 else np.full((m.shape[0], 1), np.nan)
     var = (v[:, :1] + nu / (nu - 2.0) * np.exp(m[:, 1:2] + 0.5 * v[:, 1:2])) if nu > 2.0 else np.full((m.shape[0], 1), np.inf)
     return mean, var
-
-
-def install(monkeypatch):
-    """Dispatch "Student" in the oracle's likelihood module to this file; every other family keeps the original."""
-    from oracle import likelihoods_oracle as lo
-    orig_var_exp_all, orig_dim_f = lo.var_exp_all, lo.dim_f
-
-    def var_exp_all(name, y, m, v, exact=False, **kw):
-        if name == "Student":
-            return var_exp(y, m, v, **kw)
-        return orig_var_exp_all(name, y, m, v, exact=exact, **kw)
-
-    def dim_f(name, K=None):
-        return 2 if name == "Student" else orig_dim_f(name, K)
-
-    monkeypatch.setattr(lo, "var_exp_all", var_exp_all)
-    monkeypatch.setattr(lo, "dim_f", dim_f)

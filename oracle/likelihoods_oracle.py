@@ -1,4 +1,7 @@
-"""TEST INFRASTRUCTURE ONLY -- NumPy restatement of the reference's variational expectations.
+"""TEST INFRASTRUCTURE ONLY -- NumPy restatement of the variational expectations of all eleven likelihood families.
+
+Eight families (ids 0-7) restate the reference; Student, Ordinal and Dirichlet (ids 8-10), of which the reference ships constructors
+only, restate the project's own contracts of DESIGN 9, 9b and 9d in `lik_student.py`, `lik_ordinal.py` and `lik_dirichlet.py`.
 
 CPU oracle for rows L1-L8 / A6 of SURVEY.md section 8(a).  Only `tests/`, `__graft_entry__.smoke()`
 and `bench.py`'s `cpu_baseline` leg may import this; the product path (`hetmogp_amd/`) never does.
@@ -7,7 +10,7 @@ Pinned against `tests/golden/lik_*.npz`, which were produced by the reference's 
 
 Each function returns `(ve (N,), dm (N,dim_f), dv (N,dim_f))` where
   ve = E_q[log p(y|f)],  dm = d ve / d m,  dv = d ve / d v      (q(f) = N(m, diag v))
-exactly as the reference computes them -- including its quirks:
+exactly as the reference computes them (the three contract families: as their contract defines them) -- including its quirks:
   Q1  Gamma/Beta divide the Gauss-Hermite weights by sqrt(pi) twice (gamma.py:110,139-141,152,186-189;
       beta.py:113,142-144,155,189-192): all three outputs are 1/pi times the true 2-D quadrature.
   Q2  Categorical dm is the constant onehot(y)[d] - 1 (categorical.py:102-113).
@@ -16,10 +19,14 @@ Likelihood ids (shared with include/hetmogp_hip.h):
 import numpy as np
 from scipy import special
 
-LIK_GAUSSIAN, LIK_BERNOULLI, LIK_HETGAUSSIAN, LIK_CATEGORICAL, LIK_POISSON, LIK_EXPONENTIAL, LIK_GAMMA, LIK_BETA = range(8)
+from . import lik_dirichlet, lik_ordinal, lik_student
+
+(LIK_GAUSSIAN, LIK_BERNOULLI, LIK_HETGAUSSIAN, LIK_CATEGORICAL, LIK_POISSON, LIK_EXPONENTIAL, LIK_GAMMA, LIK_BETA, LIK_STUDENT,
+ LIK_ORDINAL, LIK_DIRICHLET) = range(11)
 LIK_IDS = dict(Gaussian=LIK_GAUSSIAN, Bernoulli=LIK_BERNOULLI, HetGaussian=LIK_HETGAUSSIAN,
                Categorical=LIK_CATEGORICAL, Poisson=LIK_POISSON, Exponential=LIK_EXPONENTIAL, Gamma=LIK_GAMMA,
-               Beta=LIK_BETA)
+               Beta=LIK_BETA, Student=LIK_STUDENT, Ordinal=LIK_ORDINAL, Dirichlet=LIK_DIRICHLET)
+_CONTRACT = dict(Student=lik_student, Ordinal=lik_ordinal, Dirichlet=lik_dirichlet)
 
 _LIM_VAL = np.log(np.finfo(np.float64).max)   # GPy safe_exp clip
 _SQRT_MAX = np.sqrt(np.finfo(np.float64).max)  # GPy safe_square clip
@@ -30,7 +37,9 @@ def dim_f(name, K=None):
     """Number of latent parameter functions of a likelihood (`*/get_metadata`)."""
     if name == "Categorical":
         return K - 1
-    return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2)[name]
+    if name == "Dirichlet":
+        return int(K)
+    return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1)[name]
 
 
 def safe_exp(f):
@@ -208,7 +217,11 @@ def categorical(y, m, v, K, T=10, chunk=256, exact_dm=False):
 def var_exp_all(name, y, m, v, exact=False, **kw):
     """Dispatch on the reference's class name (het_likelihood.py:101-131 loops these per task).  exact=True is NOT the
     reference: it removes quirk Q1 (the extra 1/pi of Gamma / Beta) and quirk Q2 (Categorical's constant d/dm) so that
-    (dm, dv) are the true derivatives of ve -- the yardstick of the engine's quirks = "exact" mode."""
+    (dm, dv) are the true derivatives of ve -- the yardstick of the engine's quirks = "exact" mode.  Student, Ordinal and
+    Dirichlet have no quirks: exact=True is the same as the reference mode for them.  **kw are the keyword arguments the specs
+    carry (deg_free; K, bin_edges, sigma; K)."""
+    if name in _CONTRACT:
+        return _CONTRACT[name].var_exp(y, m, v, **kw)
     if name == "Gaussian":
         return gaussian(y, m, v, kw.get("sigma", 0.5) if kw.get("sigma", None) is not None else 0.5)
     if name == "Categorical":
@@ -226,7 +239,12 @@ def predictive(name, m, v, gh_T=None, **kw):
     Returns (mean_pred (N, dim_p), var_pred (N, dim_p)).  gh_T = Gauss-Hermite order the instance would use: 20 on a
     fresh instance, 10 for Gamma/Beta whose var_exp ran first (quirk Q7); Categorical always 10.
     References: gaussian.py:64-67, bernoulli.py:113-128, hetgaussian.py:75-88, poisson.py:97-112, exponential.py:101-116,
-    gamma.py:196-238, beta.py:199-241 (both 1/pi-scaled, quirk Q1), categorical.py:224-269 (variance 'NOT IMPLEMENTED')."""
+    gamma.py:196-238, beta.py:199-241 (both 1/pi-scaled, quirk Q1), categorical.py:224-269 (variance 'NOT IMPLEMENTED').
+    Student and Ordinal are closed forms (gh_T unused); Dirichlet takes the gh_T^K tensor rule, 20 unless told otherwise."""
+    if name in ("Student", "Ordinal"):
+        return _CONTRACT[name].predictive(m, v, **kw)
+    if name == "Dirichlet":
+        return lik_dirichlet.predictive(m, v, gh_T=gh_T or 20, **kw)
     N = m.shape[0]
     if name == "Gaussian":
         s = kw.get("sigma", 0.5)

@@ -227,19 +227,15 @@ def _eval(job):
 
 
 def oracle_rows(spec, y, m, v, param, exact=False):
-    """The float64 oracle (tests/student_ref.py for Student) on the grid, [N, 1 + 2 J], grouped by the per-row parameter."""
+    """The float64 oracle on the grid, [N, 1 + 2 J], grouped by the per-row parameter."""
     from oracle import likelihoods_oracle as lo
-    import student_ref
     out = np.empty((y.shape[0], 1 + 2 * m.shape[1]))
     keys = param if spec[2] else np.zeros_like(param)
     for p in np.unique(keys):
         idx = np.where(keys == p)[0]
         kw = _kw(spec, float(p))
         with np.errstate(all="ignore"):
-            if spec[0] == "Student":
-                ve, dm, dv = student_ref.var_exp(y[idx], m[idx], v[idx], **kw)
-            else:
-                ve, dm, dv = lo.var_exp_all(spec[0], y[idx, None], m[idx], v[idx], exact=exact, **kw)
+            ve, dm, dv = lo.var_exp_all(spec[0], y[idx, None], m[idx], v[idx], exact=exact, **kw)
         out[idx] = np.concatenate([np.reshape(ve, (-1, 1)), np.reshape(dm, (len(idx), -1)), np.reshape(dv, (len(idx), -1))], 1)
     return out
 

@@ -11,7 +11,7 @@ A = sum_k a_k):
   dm_k:  W a_k psi(A) per node;  -w_i a_k(i) psi(a_k(i)),  w_i a_k(i) log y_k  per i
   dv_k:  half of: the addends of dm_k,  W a_k^2 psi'(A) per node,  -w_i a_k(i)^2 psi'(a_k(i)) per i
 
-Independent of the float64 code (imports neither hetmogp_amd nor dirichlet_ref).  The clip bounds and LIM are the float64 numbers of the
+Independent of the float64 code (imports neither hetmogp_amd nor lik_dirichlet).  The clip bounds and LIM are the float64 numbers of the
 contract.  psi' is evaluated by its recurrence and asymptotic series here (mpmath.psi(1, .) goes through the Hurwitz zeta function and
 costs twenty times as much; the two are compared in tests/test_dirichlet_cpu.py).  40 working digits: R is wanted to well below
 2^-52 S, a bound relative to the sum of the ABSOLUTE addends, which no cancellation between them touches."""

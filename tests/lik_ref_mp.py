@@ -1,7 +1,7 @@
 """High-precision restatement (mpmath, 50 digits) of the variational expectations of all nine likelihood families, written
 node by node from the formulas: the reference's eight families with their clips, `safe_exp` / `safe_square` bounds and quirks
 Q1 / Q2 (as `oracle/likelihoods_oracle.py` documents them) and the Student-t of DESIGN 9.  Independent of the float64 code:
-it imports neither the oracle nor `student_ref`.  Only `oracle/make_lik_grid.py` and `tests/test_likgrid_cpu.py` import it;
+it imports neither the oracle nor `lik_student`.  Only `oracle/make_lik_grid.py` and `tests/test_likgrid_cpu.py` import it;
 the GPU tests read the committed `tests/golden/likgrid_*.npz` instead.
 
 The Gauss-Hermite nodes x_i and normalised weights w_i = fl(w_i / sqrt(pi)) are the float64 tables the kernels carry

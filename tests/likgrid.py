@@ -6,7 +6,7 @@ R = the 50-digit value of the reference's rule, S = its condition scale (sum ove
 of the addends; tests/lik_ref_mp.py), both from the fixture -- never an array maximum.  Needs NumPy only.
 
 Constants.  C_ORACLE[(family, mode)][class] = (ve, dm, dv): the largest |oracle - R| / (2^-52 S) of the float64 NumPy oracle
-(tests/student_ref.py for Student) over the committed grids, per output kind and row class, rounded up to the next power of
+(oracle/lik_student.py for Student) over the committed grids, per output kind and row class, rounded up to the next power of
 two -- what plain float64 with libm / SciPy special functions achieves on the reference's formulas.  The two classes are kept
 apart (the amplification of the rounding of f = m + sqrt(2 v) x_i by |f| in exp(f), and of the rounding of p by 1 / (1 - p) in
 log(1 - p), is NOT folded into S): "bulk" = m in [-3, 3], v in [1e-3, 4]; "edge" = every designed row.  The kernels get

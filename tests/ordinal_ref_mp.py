@@ -10,7 +10,7 @@ Addends of one node, with a = (lo - f) / sigma, b = (hi - f) / sigma, P = Phi(b)
   dlog p/df:    phi(a) / (sigma P),   -phi(b) / (sigma P)
   d2log p/df2:  a phi(a) / (sigma^2 P),   -b phi(b) / (sigma^2 P),   -(dlog p/df)^2       (terms with an infinite a or b are 0)
 
-Independent of the float64 code (imports neither hetmogp_amd nor ordinal_ref).  Precision: P itself needs two rewrites that no
+Independent of the float64 code (imports neither hetmogp_amd nor lik_ordinal).  Precision: P itself needs two rewrites that no
 number of digits buys back -- in the upper tail Phi(b) - Phi(a) is 1 - 1 to 10^5 digits -- so the bin is mirrored onto the lower
 side and a bin that straddles f is 1 - (two tails); after that the only cancellation left is a narrow bin's (6 digits at 1e-6
 sigma), and 120 working digits are ample for results rounded to 50."""

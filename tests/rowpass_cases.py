@@ -30,7 +30,7 @@ def dense_latent(tag):
 
 def dense_case(tag):
     """(prm, prob, X, Y, forced_rungs) of one case."""
-    from test_gpu_engine import synth
+    from model_cases import synth
     c = CASES[tag]
     # F (one latent): 100 h at M = 1024 is a tenth of the input range and K^ falls to e^-50 across it (min|H| / max|H| = 3.9e-12, far
     # tiles numerically zero again); it takes the ABSOLUTE lengthscale of case D's dense latent instead, 100 / 383 = 267 h
@@ -42,7 +42,7 @@ def dense_case(tag):
 
 def banded_case(M=384, Ns=(1030, 515, 17)):
     """The EXISTING style of case (lengthscale about one inducing spacing, free ladder) at case D's shape."""
-    from test_gpu_engine import synth
+    from model_cases import synth
     return synth(50 + M, SPECS[:len(Ns)], list(Ns), M, 2, 1, (1.0, 1.25))
 
 

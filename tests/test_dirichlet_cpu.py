@@ -1,9 +1,9 @@
 """CPU: the Dirichlet likelihood of DESIGN 9d at the layers that need no device -- the C enum and limit, the ctypes ids, the
 descriptor, its metadata with a multi-column Y, the synthetic generator -- and the yardstick itself: the float64 restatement
-tests/dirichlet_ref.py against the high-precision one (tests/dirichlet_ref_mp.py) on the committed grid tests/golden/dirgrid.npz,
+oracle/lik_dirichlet.py against the high-precision one (tests/dirichlet_ref_mp.py) on the committed grid tests/golden/dirgrid.npz,
 under the criterion of tests/likgrid.py,  |got - R| <= C 2^-52 S  per element.
 
-C_ORACLE: the largest |dirichlet_ref - R| / (2^-52 S) over the committed grid per row class and output kind (ve, dm, dv), rounded
+C_ORACLE: the largest |lik_dirichlet - R| / (2^-52 S) over the committed grid per row class and output kind (ve, dm, dv), rounded
 up to a power of two.  Measured 2026-10-17 (NumPy / SciPy on the CPU), raw figures:
     bulk   1.22 / 1.06 / 1.40          edge   1.35 / 2.85 / 1.36
 No element of the grid is non-finite, no element is excepted, no bulk row is above the bulk constants."""
@@ -15,7 +15,7 @@ import mpmath
 import numpy as np
 import pytest
 
-import dirichlet_ref
+from oracle import lik_dirichlet
 import dirichlet_ref_mp
 import likgrid
 
@@ -157,7 +157,7 @@ def test_float64_restatement_against_high_precision_grid():
     """Where C_ORACLE comes from; also the three conditions on the restatement: no non-finite element, no exception list, no
     bulk row above the bulk constants (assert_grid applies the bulk constants to every bulk row and takes no exceptions)."""
     g = load_grid()
-    w = assert_grid(g, evaluate(g, dirichlet_ref.var_exp), C_ORACLE, "dirichlet_ref on dirgrid")
+    w = assert_grid(g, evaluate(g, lik_dirichlet.var_exp), C_ORACLE, "lik_dirichlet on dirgrid")
     for c in (BULK, EDGE):                                                         # the constants are the measured figures, rounded up
         for k in range(3):
             assert w[c][k] > C_ORACLE[c][k] / 2.0, (c, k, w[c][k])
@@ -166,7 +166,7 @@ def test_float64_restatement_against_high_precision_grid():
 def test_float64_scale_matches_high_precision_scale():
     g = load_grid()
     for K, idx in grid_groups(g):
-        S = dirichlet_ref.var_exp_scale(g["y"][idx, :K], g["m"][idx, :K], g["v"][idx, :K], K)
+        S = lik_dirichlet.var_exp_scale(g["y"][idx, :K], g["m"][idx, :K], g["v"][idx, :K], K)
         assert np.allclose(S, g["S"][idx, :1 + 2 * K], rtol=1e-12, atol=0), K
 
 
@@ -204,8 +204,8 @@ def test_k2_is_the_oracle_s_beta_in_exact_mode():
     y1 = y2[:, 0]
     y2 = np.stack([y1, 1.0 - y1], 1)
     want = likgrid.pack(*lo.var_exp_all("Beta", y1, m, v, exact=True), N)
-    got = likgrid.pack(*dirichlet_ref.var_exp(y2, m, v, K=2), N)
-    S = dirichlet_ref.var_exp_scale(y2, m, v, 2)
+    got = likgrid.pack(*lik_dirichlet.var_exp(y2, m, v, K=2), N)
+    S = lik_dirichlet.var_exp_scale(y2, m, v, 2)
     C = np.array(C_ORACLE[BULK])[kind_of(2)] + np.array(likgrid.c_oracle("Beta", "exact")[BULK])[kind_of(2)]
     r = np.abs(got - want) / (likgrid.EPS * S)
     relerr = np.max(np.abs(got - want) / np.abs(want), 0)
@@ -218,9 +218,9 @@ def test_k2_is_the_oracle_s_beta_in_exact_mode():
 def test_decomposed_form_is_the_full_tensor_sum(K):
     """The contract's form differs from the plain tensor sum of log p and its derivatives by (sum(w) - 1) per dimension only."""
     y, m, v = _bulk(np.random.RandomState(K), 12, K)
-    a = likgrid.pack(*dirichlet_ref.var_exp(y, m, v, K), 12)
-    b = likgrid.pack(*dirichlet_ref.var_exp_full(y, m, v, K), 12)
-    S = dirichlet_ref.var_exp_scale(y, m, v, K)
+    a = likgrid.pack(*lik_dirichlet.var_exp(y, m, v, K), 12)
+    b = likgrid.pack(*lik_dirichlet.var_exp_full(y, m, v, K), 12)
+    S = lik_dirichlet.var_exp_scale(y, m, v, K)
     assert np.all(np.abs(a - b) <= 64.0 * likgrid.EPS * S)
 
 
@@ -232,9 +232,9 @@ def test_derivatives_are_those_of_ve(K):
     N = 4
     y, m, _ = _bulk(rng, N, K)
     m, v = 0.5 * m, np.exp(rng.uniform(np.log(1e-3), np.log(0.5), (N, K)))
-    _, dm, dv = dirichlet_ref.var_exp(y, m, v, K)
+    _, dm, dv = lik_dirichlet.var_exp(y, m, v, K)
     h = 1e-4
-    fine = lambda mm, vv: dirichlet_ref.var_exp(y, mm, vv, K, T=16)[0]
+    fine = lambda mm, vv: lik_dirichlet.var_exp(y, mm, vv, K, T=16)[0]
     worst = 0.0
     for k in range(K):
         e = np.zeros(K)
@@ -259,7 +259,7 @@ def test_outputs_are_finite_at_the_extremes():
                     y[0, 0] = tiny
                     m = np.full((1, K), 0.3)
                     m[0, K - 1] = m0
-                    out = likgrid.pack(*dirichlet_ref.var_exp(y, m, np.full((1, K), v0), K), 1)
+                    out = likgrid.pack(*lik_dirichlet.var_exp(y, m, np.full((1, K), v0), K), 1)
                     assert np.all(np.isfinite(out)), (K, m0, v0, tiny)
 
 
@@ -269,10 +269,10 @@ def test_predictive_means_sum_to_one(K):
     N = 8 if K == 4 else 40
     m, v = rng.uniform(-3.0, 3.0, (N, K)), np.exp(rng.uniform(np.log(1e-3), np.log(4.0), (N, K)))
     for T in (10, 20) if K < 4 else (10,):
-        mean, var = dirichlet_ref.predictive(m, v, K, gh_T=T)
+        mean, var = lik_dirichlet.predictive(m, v, K, gh_T=T)
         assert mean.shape == (N, K) and np.all(mean > 0.0) and np.all(var > 0.0)
         assert np.max(np.abs(mean.sum(1) - 1.0)) <= 16 * likgrid.EPS                           # (sum(w))^K = 1 to rounding
     # v = 0: the moments at f = m
-    mean, var = dirichlet_ref.predictive(m, np.zeros_like(m), K, gh_T=10)
-    mu, vr = dirichlet_ref.moments(m)
+    mean, var = lik_dirichlet.predictive(m, np.zeros_like(m), K, gh_T=10)
+    mu, vr = lik_dirichlet.moments(m)
     assert np.allclose(mean, mu, rtol=1e-13, atol=0) and np.allclose(var, vr, rtol=1e-9, atol=1e-16)

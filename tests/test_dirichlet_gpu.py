@@ -1,9 +1,8 @@
 """GPU: the Dirichlet likelihood of DESIGN 9d through every layer -- the wave-per-row quadrature against the high-precision grid
 tests/golden/dirgrid.npz (criterion and constants: tests/test_dirichlet_cpu.py) and against the float64 restatement
-tests/dirichlet_ref.py, the predictive moments, sampling statistics, the Monte-Carlo log predictive, the refusal of an invalid K and of
-rows off the open simplex, the whole ELBO + gradient against the unchanged oracle (its likelihood dispatch monkeypatched to the
-restatement for "Dirichlet") on the default, several-pool, minibatch, small-model, no-small-path and strict q(f) paths, and the model
-facade end to end.
+oracle/lik_dirichlet.py, the predictive moments, sampling statistics, the Monte-Carlo log predictive, the refusal of an invalid K and of
+rows off the open simplex, the whole ELBO + gradient against the oracle (the checks of tests/model_cases.py) on the
+default, several-pool, minibatch, small-model, no-small-path and strict q(f) paths, and the model facade end to end.
 
 Kernel bounds = max(16, 4 C_ORACLE) of tests/test_dirichlet_cpu.py: 16 for every class and output kind.  Measured on one MI355X,
 2026-10-17, largest |got - R| / (2^-52 S), ve / dm / dv:
@@ -15,20 +14,14 @@ import numpy as np
 import pytest
 from scipy import stats
 
-import dirichlet_ref
 import likgrid
+import model_cases as mc
 import test_dirichlet_cpu as dc
-from conftest import assert_parity
+from oracle import lik_dirichlet
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ["elbo", "g_m_u", "g_L_u", "g_variance", "g_lengthscale", "g_W", "g_kappa", "g_Z"]
 NAN = float("nan")
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
 
 
 def _gpu_var_exp(y, m, v, **kw):
@@ -62,8 +55,8 @@ def test_var_exp_matches_restatement(K, N):
     got = _gpu_var_exp(y, m, v, K=K)
     assert got[0].shape == (N,) and got[1].shape == (N, K) and got[2].shape == (N, K)
     got = likgrid.pack(*got, N)
-    want = likgrid.pack(*dirichlet_ref.var_exp(y, m, v, K), N)
-    r = np.abs(got - want) / (likgrid.EPS * dirichlet_ref.var_exp_scale(y, m, v, K))
+    want = likgrid.pack(*lik_dirichlet.var_exp(y, m, v, K), N)
+    r = np.abs(got - want) / (likgrid.EPS * lik_dirichlet.var_exp_scale(y, m, v, K))
     print("K = %d N = %d: worst |kernel - restatement| / (2^-52 S) = %.3g" % (K, N, r.max()))
     assert np.all(np.isfinite(got)) and np.all(r <= C[None, :]), (K, N, r.max(0))
     from hetmogp_amd import Dirichlet
@@ -101,7 +94,7 @@ def test_predictive_against_restatement(K, T):
     m, v = rng.uniform(-3.0, 3.0, (N, K)), np.exp(rng.uniform(np.log(1e-3), np.log(4.0), (N, K)))
     mean, var = predictive("Dirichlet", m, v, gh_T=T, K=K)
     assert mean.shape == (N, K) and var.shape == (N, K) and np.all(np.isfinite(mean)) and np.all(var > 0.0)
-    wm, wv = dirichlet_ref.predictive(m, v, K, gh_T=T)
+    wm, wv = lik_dirichlet.predictive(m, v, K, gh_T=T)
     rm = np.abs(mean - wm) / (likgrid.EPS * wm)
     Sv = wv + 2.0 * wm * wm
     rv = (np.abs(var - wv) - 4.0 * likgrid.EPS) / (likgrid.EPS * Sv)
@@ -124,8 +117,8 @@ def test_sample_moments():
         K = len(f)
         Y = sample("Dirichlet", np.tile(np.array(f), (N, 1)), seed=300 + seed, K=K)
         assert Y.shape == (N, K) and np.all(np.isfinite(Y)) and np.all(Y >= 0.0) and np.max(np.abs(Y.sum(1) - 1.0)) < 1e-12
-        mu, vr = dirichlet_ref.moments(np.array(f))
-        a = dirichlet_ref.alpha_of(np.array(f))
+        mu, vr = lik_dirichlet.moments(np.array(f))
+        a = lik_dirichlet.alpha_of(np.array(f))
         kurt = np.array([float(stats.beta(ak, a.sum() - ak).stats("k")) for ak in a])
         zm = np.abs(Y.mean(0) - mu) / np.sqrt(vr / N)
         zv = np.abs(Y.var(0) - vr) / (vr * np.sqrt((kurt + 2.0) / N))
@@ -148,18 +141,18 @@ def test_log_predictive():
         y, m, _ = _bulk(rng, N, K)
         m = rng.uniform(-25.0, 25.0, (N, K))                                   # both clips of alpha included
         got = log_predictive_rows("Dirichlet", y, m, np.zeros((N, K)), num_samples=128, seed=4, K=K)
-        want = dirichlet_ref.logpdf(y, m)                                      # v = 0: every sample is f = m
+        want = lik_dirichlet.logpdf(y, m)                                      # v = 0: every sample is f = m
         assert got.shape == (N,) and np.all(np.isfinite(got))
         assert np.max(np.abs(got - want) / np.maximum(1.0, np.abs(want))) < 1e-10, K
         # v > 0: the kernel's estimate and the restatement's are two independent Monte-Carlo estimates of the same number from S
         # samples each, so they differ by less than 5 standard errors of their difference, sqrt 2 times the restatement's own
         # (observations drawn from the model at a draw of f, so that neither estimator is a rare-event one)
         m2, v2 = rng.uniform(-1.5, 1.5, (N, K)), 10.0 ** rng.uniform(-2.0, -0.5, (N, K))
-        y2 = np.maximum(dirichlet_ref.samples(m2 + np.sqrt(v2) * rng.randn(N, K), rng), 1e-12)
+        y2 = np.maximum(lik_dirichlet.samples(m2 + np.sqrt(v2) * rng.randn(N, K), rng), 1e-12)
         y2 = y2 / y2.sum(1, keepdims=True)
         S = 8192
         got = log_predictive_rows("Dirichlet", y2, m2, v2, num_samples=S, seed=9, K=K)
-        est, se = dirichlet_ref.log_predictive_rows(y2, m2, v2, S, np.random.RandomState(1), K)
+        est, se = lik_dirichlet.log_predictive_rows(y2, m2, v2, S, np.random.RandomState(1), K)
         z = np.abs(got - est) / (np.sqrt(2.0) * se)
         print("log predictive K = %d: worst |kernel - restatement| / se of the difference = %.2f" % (K, z.max()))
         assert np.all(np.abs(got - est) <= 5.0 * np.sqrt(2.0) * se + 1e-12), (K, z.max())
@@ -233,109 +226,28 @@ SET_DDG = [DIR(2), DIR(3), ("Gaussian", {"sigma": 0.7})]
 SET_D4G = [DIR(4), ("Gaussian", {"sigma": 0.5})]
 
 
-def _case(seed, specs, Ns, M, Q, P):
-    """Seeded case built by the engine suite's generator (call after dirichlet_ref.install: the oracle's dim_f knows the family then);
-    the Dirichlet tasks' observations are replaced by compositions, (N, K)."""
-    from oracle import svmogp_oracle as so
-    from test_gpu_engine import synth
-    prm, _, X, Y = synth(seed, specs, Ns, M, Q, P, tuple(0.9 + 0.15 * q for q in range(Q)))
-    rng = np.random.RandomState(seed + 1)
-    for t, (n, kw) in enumerate(specs):
-        if n == "Dirichlet":
-            y = np.maximum(rng.dirichlet(np.full(kw["K"], 1.5), Ns[t]), 1e-9)
-            Y[t] = y / y.sum(1, keepdims=True)
-    return prm, so.make_problem(specs, Q, M, P), X, Y
-
-
-def _engine(prob, X, Y, **kw):
-    from hetmogp_amd.engine import Engine
-    e = Engine(prob["specs"], prob["Q"], prob["M"], prob["P"], **kw)
-    e.set_data(X, Y)
-    return e
-
-
-def _run(e, prm, bs=None, **kw):
-    args = dict(Z=prm["Z"], m_u=prm["m_u"], L_flat=prm["L_flat"], variance=prm["variance"], lengthscale=prm["lengthscale"],
-                W=prm["W"], kappa=prm["kappa"], batch_scale=bs)
-    args.update(kw)
-    return e.elbo_grad(**args)
-
-
 CASES = [(SET_GDB, 128, 2, 1), (SET_GDB, 128, 2, 2), (SET_DDG, 128, 2, 1), (SET_D4G, 128, 2, 1)]
 
 
 @pytest.mark.parametrize("specs,M,Q,P", CASES, ids=["%s-M%d-Q%d-P%d" % ("+".join(n + str(k.get("K", "")) for n, k in c[0]), c[1], c[2], c[3])
                                                      for c in CASES])
-def test_elbo_grad_vs_oracle(monkeypatch, specs, M, Q, P):
-    """The default path with one row pool and with several (chunk_rows below the row count), then a minibatch whose row_begin > 0 and
-    whose slice is shorter than the task: the [K][N_t] array of log y_k is read with the TASK's stride there, not the slice's."""
-    from oracle import svmogp_oracle as so
-    dirichlet_ref.install(monkeypatch)
+def test_elbo_grad_vs_oracle(specs, M, Q, P):
+    """In the minibatch the [K][N_t] array of log y_k is read with the TASK's stride, not the slice's."""
     Ns = [300, 257, 129][:len(specs)]
-    prm, prob, X, Y = _case(2100 + M + 7 * Q + P, specs, Ns, M, Q, P)
-    want = so.elbo_grad_fused(prm, prob, X, Y)
-    e1, e2 = _engine(prob, X, Y), _engine(prob, X, Y, chunk_rows=97)
-    for e in (e1, e2):
-        out = _run(e, prm)
-        for k in KEYS:
-            assert_parity(out[k], want[k], k)
-    rb = [n // 5 for n in Ns]
-    re = [min(n, b + max(1, n // 3)) for n, b in zip(Ns, rb)]
-    bs = [float(n) / (e_ - b) for n, b, e_ in zip(Ns, rb, re)]
-    wantb = so.elbo_grad_fused(prm, prob, [x[b:e_] for x, b, e_ in zip(X, rb, re)], [y[b:e_] for y, b, e_ in zip(Y, rb, re)],
-                               batch_scale=bs)
-    for e in (e1, e2):
-        outb = _run(e, prm, bs, row_begin=rb, row_end=re)
-        for k in KEYS:
-            assert_parity(outb[k], wantb[k], "minibatch " + k)
-    e1.close(), e2.close()
+    mc.check_vs_oracle(mc.family_case(2100 + M + 7 * Q + P, specs, Ns, M, Q, P), Ns)
 
 
 @pytest.mark.parametrize("specs", [SET_GDB, SET_DDG], ids=["Gaussian+Dirichlet3+Bernoulli", "Dirichlet2+Dirichlet3+Gaussian"])
-def test_small_model_path_and_no_small_path(monkeypatch, specs):
-    """M = 16: the fused small-model kernels (their hipGraph is the witness: only that path captures one) launch the same quadrature,
-    all segments in one launch_quad_multi pass over one segment table (one dispatch per family present: a set outside the baseline
-    masks takes the singleton instantiations) -- the second set is two Dirichlet segments with different K beside a Gaussian one --
-    and replay it from the graph; HMOGP_CFG_NO_SMALL_PATH runs the regular kernels on the same model.  A minibatch on the small path
-    too (row_begin > 0)."""
-    from oracle import svmogp_oracle as so
-    dirichlet_ref.install(monkeypatch)
+def test_small_model_path_and_no_small_path(specs):
+    """M = 16: all segments in one launch_quad_multi pass over one segment table (one dispatch per family present: a set outside the
+    baseline masks takes the singleton instantiations) -- the second set is two Dirichlet segments with different K beside a Gaussian
+    one; HMOGP_CFG_NO_SMALL_PATH runs the regular kernels on the same model."""
     Ns = [300, 257, 129]
-    prm, prob, X, Y = _case(277, specs, Ns, 16, 2, 1)
-    want = so.elbo_grad_fused(prm, prob, X, Y)
-    es, er = _engine(prob, X, Y), _engine(prob, X, Y, small_path=False)
-    for _ in range(3):
-        a, b = _run(es, prm), _run(er, prm)
-    assert es.graph_stats()[0] >= 1 and er.graph_stats() == (0, 0), (es.graph_stats(), er.graph_stats())
-    worst = {k: rel(a[k], b[k]) for k in KEYS}
-    print("small vs regular path, relative difference per array:", {k: "%.1e" % x for k, x in worst.items()})
-    assert worst["elbo"] < 1e-12, worst
-    for k in KEYS:
-        assert worst[k] < 1e-10, (k, worst[k])
-        assert_parity(a[k], want[k], k)
-        assert_parity(b[k], want[k], "no small path " + k)
-    rb, re = [60, 50, 20], [160, 137, 129]
-    bs = [float(n) / (e_ - b) for n, b, e_ in zip(Ns, rb, re)]
-    wantb = so.elbo_grad_fused(prm, prob, [x[b:e_] for x, b, e_ in zip(X, rb, re)], [y[b:e_] for y, b, e_ in zip(Y, rb, re)],
-                               batch_scale=bs)
-    for _ in range(2):
-        outb = _run(es, prm, bs, row_begin=rb, row_end=re)
-    for k in KEYS:
-        assert_parity(outb[k], wantb[k], "small-path minibatch " + k)
-    es.close(), er.close()
+    mc.check_small_vs_regular(mc.family_case(277, specs, Ns, 16, 2, 1), Ns, ([60, 50, 20], [160, 137, 129]))
 
 
-def test_strict_qf_vs_literal_oracle(monkeypatch):
-    from oracle import svmogp_oracle as so
-    dirichlet_ref.install(monkeypatch)
-    prm, prob, X, Y = _case(231, SET_DDG, [300, 257, 129], 128, 2, 1)
-    lit = so.elbo_grad_literal(prm, prob, X, Y)
-    e = _engine(prob, X, Y, strict_qf=True)
-    out = _run(e, prm)
-    assert out["rungs"] == [-1, -1]
-    for k in KEYS:
-        assert_parity(out[k], lit[k], k)
-    e.close()
+def test_strict_qf_vs_literal_oracle():
+    mc.check_strict_vs_literal(mc.family_case(231, SET_DDG, [300, 257, 129], 128, 2, 1))
 
 
 # ------------------------------------------------------------------------------------------------ facade end to end

@@ -7,14 +7,9 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, elementwise_excess
+from conftest import GOLDEN, elementwise_excess, rel_norm as rel
 
 pytestmark = pytest.mark.gpu
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
 
 
 def build_model(g, batch_size=None, **model_kw):

@@ -9,15 +9,10 @@ import numpy as np
 import pytest
 import scipy.linalg
 
-from conftest import GOLDEN
+from conftest import GOLDEN, rel_norm as rel
 import likgrid
 
 pytestmark = pytest.mark.gpu
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
 
 
 @pytest.fixture(scope="module")

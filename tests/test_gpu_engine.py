@@ -10,31 +10,12 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, elementwise_excess
+from conftest import GOLDEN, elementwise_excess, rel_norm as rel
+from model_cases import KEYS, make_engine, run, synth
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ["elbo", "g_m_u", "g_L_u", "g_variance", "g_lengthscale", "g_W", "g_kappa", "g_Z"]
 TOL = 1e-8
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
-
-
-def make_engine(prob, X, Y, **kw):
-    from hetmogp_amd.engine import Engine
-    e = Engine(prob["specs"], prob["Q"], prob["M"], prob["P"], **kw)
-    e.set_data(X, Y)
-    return e
-
-
-def run(e, prm, bs=None, **kw):
-    args = dict(Z=prm["Z"], m_u=prm["m_u"], L_flat=prm["L_flat"], variance=prm["variance"],
-                lengthscale=prm["lengthscale"], W=prm["W"], kappa=prm["kappa"], W0=prm.get("W0"), batch_scale=bs)
-    args.update(kw)
-    return e.elbo_grad(**args)
 
 
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "model_*.npz"))), ids=os.path.basename)
@@ -87,43 +68,6 @@ def test_engine_vs_reference_inference(path):
                 assert rel(v[:, d], g["v_fd_%d" % d][:, 0]) < TOL
                 assert elementwise_excess(m[:, d], g["m_fd_%d" % d][:, 0]) <= 1.0
                 assert elementwise_excess(v[:, d], g["v_fd_%d" % d][:, 0]) <= 1.0
-
-
-def synth(seed, specs, Ns, M, Q, P, cs):
-    """Seeded synthetic case in the style of the fixtures (oracle/make_golden.py:build_case)."""
-    from oracle import svmogp_oracle as so
-    rng = np.random.RandomState(seed)
-    prob = so.make_problem(specs, Q, M, P)
-    Df = prob["Df"]
-    X = [np.sort(rng.rand(n, P), axis=0) if P == 1 else rng.rand(n, P) for n in Ns]
-    Y = []
-    for (name, kw), n in zip(specs, Ns):
-        if name in ("Gaussian", "HetGaussian"):
-            Y.append(rng.randn(n, 1))
-        elif name == "Bernoulli":
-            Y.append((rng.rand(n, 1) < 0.5).astype(float))
-        elif name == "Poisson":
-            Y.append(rng.poisson(3.0, (n, 1)).astype(float))
-        elif name in ("Gamma", "Exponential"):
-            Y.append(rng.gamma(2.0, 1.0, (n, 1)) + 1e-3)
-        elif name == "Beta":
-            Y.append(np.clip(rng.beta(2.0, 3.0, (n, 1)), 1e-4, 1 - 1e-4))
-        else:
-            Y.append(rng.randint(1, kw["K"] + 1, (n, 1)).astype(float))
-    h = 1.0 / max(M - 1, 1) if P == 1 else M ** (-1.0 / P)
-    if P == 1:
-        base = np.linspace(0, 1, M)[:, None]
-    else:                      # regular grid (random inducing points make cond(K_uu) ~ 1e6: conditioning-limited parity)
-        gsz = int(np.ceil(M ** (1.0 / P)))
-        base = np.stack(np.meshgrid(*[np.linspace(0, 1, gsz)] * P, indexing="ij"), -1).reshape(-1, P)[:M]
-        h = 1.0 / (gsz - 1)
-    Z = np.tile(base, (1, Q)) + 0.1 * h * rng.randn(M, Q * P)
-    Lfull = [np.eye(M) * (0.6 + 0.4 * rng.rand(M)) + 0.02 * np.tril(rng.randn(M, M), -1) for _ in range(Q)]
-    r, c = np.tril_indices(M)
-    prm = dict(Z=Z, m_u=rng.randn(M, Q), L_flat=np.stack([L[r, c] for L in Lfull], 1), variance=0.5 + 0.5 * rng.rand(Q),
-               lengthscale=np.array(cs) * h, W=np.where(rng.rand(Q, Df) < 0.5, 1.0, -1.0) * (0.5 + 0.3 * rng.randn(Q, Df)),
-               kappa=np.zeros((Q, Df)))
-    return prm, prob, X, Y
 
 
 def test_engine_vs_oracle_multitile():

@@ -13,7 +13,7 @@ the whole evaluation, through size-independent properties:
 import numpy as np
 import pytest
 
-from conftest import elementwise_excess
+from conftest import elementwise_excess, rel_norm as rel
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +21,6 @@ KEYS = ["elbo", "g_m_u", "g_L_u", "g_variance", "g_lengthscale", "g_W", "g_kappa
 H_SPECS = [("Gaussian", {"sigma": 0.5}), ("Bernoulli", {}), ("Poisson", {}), ("Gamma", {})]
 C4_SPECS = [("HetGaussian", {}), ("Categorical", {"K": 5}), ("Beta", {}), ("Exponential", {}), ("Gaussian", {"sigma": 0.5}),
             ("Bernoulli", {}), ("Poisson", {}), ("Gamma", {})]
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
 
 
 def check_config(specs, N, M, Q, window, seed, pools, exact_zero=True, oracle_tol=1e-8, P=1, calibrate=False):

@@ -5,7 +5,8 @@ three latents, 1-D and 2-D inputs, ragged / tiny / empty tasks, minibatch ranges
 import numpy as np
 import pytest
 
-from test_gpu_engine import KEYS, make_engine, rel, run, synth
+from conftest import rel_norm as rel
+from model_cases import KEYS, make_engine, run, synth
 
 pytestmark = pytest.mark.gpu
 

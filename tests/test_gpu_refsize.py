@@ -17,18 +17,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, assert_parity
+from model_cases import KEYS, make_engine, run
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ["elbo", "g_m_u", "g_L_u", "g_variance", "g_lengthscale", "g_W", "g_kappa", "g_Z"]
 REF = sorted(glob.glob(os.path.join(GOLDEN, "ref_*.npz")))
-
-
-def _engine(prob, X, Y, **kw):
-    from hetmogp_amd.engine import Engine
-    e = Engine(prob["specs"], prob["Q"], prob["M"], prob["P"], **kw)
-    e.set_data(X, Y)
-    return e
 
 
 def _mask(g):
@@ -49,10 +42,8 @@ def test_engine_vs_reference_run_real_size(path):
     from oracle import svmogp_oracle as so
     g = np.load(path)
     prm, prob, X, Y, bs = so.load_case(g)
-    e = _engine(prob, X, Y)
-    out = e.elbo_grad(Z=prm["Z"], m_u=prm["m_u"], L_flat=prm["L_flat"], variance=prm["variance"],
-                      lengthscale=prm["lengthscale"], W=prm["W"], kappa=prm["kappa"], W0=prm.get("W0"), batch_scale=bs,
-                      group_mask=_mask(g))
+    e = make_engine(prob, X, Y)
+    out = run(e, prm, bs, group_mask=_mask(g))
     assert out["rungs"] == [-1] * prob["Q"] and not out["v_negative"]
     for k in KEYS:
         assert_parity(out[k], g[k], k)
@@ -75,7 +66,7 @@ def test_inner_protocol_vs_reference_run_real_size(name):
     g = np.load(os.path.join(GOLDEN, name))
     prm, prob, X, Y, bs = so.load_case(g)
     prm.pop("W0", None)
-    e = _engine(prob, X, Y)
+    e = make_engine(prob, X, Y)
     out = e.elbo_grad(batch_scale=bs, **prm)
     assert_parity(out["elbo"], g["elbo_inference"], "elbo")
     raw = e.debug_raw_grads([x.shape[0] for x in X])

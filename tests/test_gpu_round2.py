@@ -10,8 +10,8 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
-from test_gpu_engine import KEYS, make_engine, rel, run, synth
+from conftest import GOLDEN, rel_norm as rel
+from model_cases import KEYS, make_engine, run, synth
 
 pytestmark = pytest.mark.gpu
 

@@ -13,8 +13,8 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, assert_parity
-from test_gpu_engine import KEYS, rel, run, synth
+from conftest import GOLDEN, assert_parity, rel_norm as rel
+from model_cases import KEYS, run, synth
 
 pytestmark = pytest.mark.gpu
 

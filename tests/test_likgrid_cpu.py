@@ -8,7 +8,6 @@ import numpy as np
 import pytest
 
 import likgrid as lg
-import student_ref
 from oracle import likelihoods_oracle as lo
 
 FILES = lg.grid_files()
@@ -17,8 +16,6 @@ IDS = [lg.tag_of(p) for p in FILES]
 
 def oracle_fn(name, y, m, v, exact=False, **kw):
     with np.errstate(all="ignore"):
-        if name == "Student":
-            return student_ref.var_exp(y, m, v, **kw)
         return lo.var_exp_all(name, y[:, None], m, v, exact=exact, **kw)
 
 

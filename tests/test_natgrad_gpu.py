@@ -11,12 +11,9 @@ Adadelta), so these are property tests:
 import numpy as np
 import pytest
 
+from conftest import rel_norm as rel
+
 pytestmark = pytest.mark.gpu
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
 
 
 def _case(specs, N, M, Q, seed):

@@ -1,9 +1,9 @@
 """CPU: the Ordinal (ordered probit) likelihood of DESIGN 9b at the layers that need no device -- the C enum and export, the
 ctypes ids, the table registry, the descriptor, its metadata, the synthetic generator -- and the yardstick itself: the float64
-restatement tests/ordinal_ref.py against the high-precision one (tests/ordinal_ref_mp.py) on the committed grid
+restatement oracle/lik_ordinal.py against the high-precision one (tests/ordinal_ref_mp.py) on the committed grid
 tests/golden/ordgrid.npz, under the criterion of tests/likgrid.py,  |got - R| <= C 2^-52 S  per element.
 
-C_ORACLE: the largest |ordinal_ref - R| / (2^-52 S) over the committed grid per row class and output kind (ve, dm, dv), rounded
+C_ORACLE: the largest |lik_ordinal - R| / (2^-52 S) over the committed grid per row class and output kind (ve, dm, dv), rounded
 up to a power of two.  Measured 2026-10-16 (NumPy / SciPy on the CPU), raw figures:
     bulk   5.59 / 4.59 / 6.92          edge   1.09e5 / 296 / 294
     predictive (mean, variance)   1.97 / 1.60
@@ -18,7 +18,7 @@ import pytest
 from scipy import special
 
 import likgrid
-import ordinal_ref
+from oracle import lik_ordinal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "hetmogp_hip.h")
@@ -161,9 +161,9 @@ def test_float64_restatement_against_high_precision_grid():
     """Where C_ORACLE comes from; also the three conditions of DESIGN 9b on the restatement: no non-finite element, no exception
     list, no bulk row above the bulk constants."""
     g = load_grid()
-    got = evaluate(g, ordinal_ref.var_exp)
+    got = evaluate(g, lik_ordinal.var_exp)
     assert np.all(np.isfinite(got))
-    w = likgrid.assert_rows(got, g["R"], g["S"], np.zeros(got.shape, np.uint8), KIND, g["cls"], C_ORACLE, "ordinal_ref on ordgrid")
+    w = likgrid.assert_rows(got, g["R"], g["S"], np.zeros(got.shape, np.uint8), KIND, g["cls"], C_ORACLE, "lik_ordinal on ordgrid")
     for c in (BULK, EDGE):                                                         # the constants are the measured figures, rounded up
         for k in range(3):
             assert w[c][k] > C_ORACLE[c][k] / 2.0, (c, k, w[c][k])
@@ -175,11 +175,11 @@ def test_predictive_restatement_against_high_precision_rows():
     got = np.empty((len(g["p_m"]), 2))
     logp = np.empty(len(g["p_m"]))
     for kw, idx in grid_groups(g, "p_"):
-        mean, var = ordinal_ref.predictive(g["p_m"][idx], g["p_v"][idx], **kw)
+        mean, var = lik_ordinal.predictive(g["p_m"][idx], g["p_v"][idx], **kw)
         got[idx] = np.concatenate([mean, var], 1)
-        logp[idx] = ordinal_ref.log_prob(g["p_y"][idx], g["p_m"][idx], g["p_v"][idx], **kw)
+        logp[idx] = lik_ordinal.log_prob(g["p_y"][idx], g["p_m"][idx], g["p_v"][idx], **kw)
     r = np.abs(got - g["p_R"]) / (likgrid.EPS * g["p_S"])
-    print("[ordgrid] predictive of ordinal_ref, worst |got - R| / (2^-52 S): mean %.3g variance %.3g" % tuple(r.max(0)))
+    print("[ordgrid] predictive of lik_ordinal, worst |got - R| / (2^-52 S): mean %.3g variance %.3g" % tuple(r.max(0)))
     assert np.all(r <= np.array(C_ORACLE_PRED))
     assert np.all(np.abs(logp - g["p_logp"]) <= 1e-12 * np.maximum(1.0, np.abs(g["p_logp"])))
 
@@ -200,17 +200,17 @@ def test_probabilities_sum_to_one_and_probit_limit():
     m, v = rng.uniform(-6.0, 6.0, N), 10.0 ** rng.uniform(-6.0, 2.0, N)
     for K, sigma in ((2, 1.0), (3, 0.3), (5, 1.0), (11, 4.0)):
         e = np.sort(rng.uniform(-4.0, 4.0, K - 1)) + 1e-3 * np.arange(K - 1)
-        P = ordinal_ref.class_probs(m, v, bin_edges=e, sigma=sigma)
+        P = lik_ordinal.class_probs(m, v, bin_edges=e, sigma=sigma)
         assert np.all(P >= 0.0) and np.max(np.abs(P.sum(1) - 1.0)) <= 4e-16 * K
     # K = 2 with b_1 = 0 is the probit Bernoulli: P(y = 2) = Phi(m / s), s = sqrt(sigma^2 + v)
     for sigma in (0.3, 1.0, 4.0):
         s = np.sqrt(sigma * sigma + v)
-        mean, var = ordinal_ref.predictive(m, v, K=2, sigma=sigma)
+        mean, var = lik_ordinal.predictive(m, v, K=2, sigma=sigma)
         p = special.ndtr(m / s)
         assert np.max(np.abs(mean[:, 0] - (1.0 + p))) <= 4e-16 and np.max(np.abs(var[:, 0] - p * (1.0 - p))) <= 1e-15
-        assert np.allclose(ordinal_ref.log_prob(np.full(N, 2.0), m, v, K=2, sigma=sigma), special.log_ndtr(m / s), rtol=1e-13, atol=0)
+        assert np.allclose(lik_ordinal.log_prob(np.full(N, 2.0), m, v, K=2, sigma=sigma), special.log_ndtr(m / s), rtol=1e-13, atol=0)
         # and var_exp's derivative at v = 0 is the probit score phi / (sigma Phi)
-        ve, dm, dv = ordinal_ref.var_exp(np.full(N, 2.0), m, np.zeros(N), K=2, sigma=sigma)
+        ve, dm, dv = lik_ordinal.var_exp(np.full(N, 2.0), m, np.zeros(N), K=2, sigma=sigma)
         assert np.allclose(ve, special.log_ndtr(m / sigma), rtol=1e-13, atol=0)
         want = np.exp(-0.5 * (m / sigma) ** 2 - special.log_ndtr(m / sigma)) / (np.sqrt(2.0 * np.pi) * sigma)
         assert np.allclose(dm[:, 0], want, rtol=1e-12, atol=0)

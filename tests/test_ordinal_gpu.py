@@ -1,8 +1,8 @@
 """GPU: the Ordinal (ordered probit) likelihood of DESIGN 9b through every layer -- the quadrature against the high-precision grid
 tests/golden/ordgrid.npz (criterion and constants: tests/test_ordinal_cpu.py) and against the float64 restatement
-tests/ordinal_ref.py, the closed-form predictive, sampling statistics, the Monte-Carlo log predictive, the refusal of invalid
-tables / ids / labels, the whole ELBO + gradient against the unchanged oracle (its likelihood dispatch monkeypatched to the
-restatement for "Ordinal") on the default, small-model, strict q(f) and minibatch paths, and the model facade end to end.
+oracle/lik_ordinal.py, the closed-form predictive, sampling statistics, the Monte-Carlo log predictive, the refusal of invalid
+tables / ids / labels, the whole ELBO + gradient against the oracle (the checks of tests/model_cases.py) on the
+default, several-pool, minibatch, small-model and strict q(f) paths, and the model facade end to end.
 
 Kernel bounds = max(16, 4 C_ORACLE) of tests/test_ordinal_cpu.py: bulk 32 / 32 / 32, edge 2^19 / 2048 / 2048 (ve / dm / dv),
 predictive 16 / 16.  Measured on one MI355X, 2026-10-16, largest |got - R| / (2^-52 S):
@@ -14,19 +14,13 @@ import numpy as np
 import pytest
 
 import likgrid
-import ordinal_ref
+import model_cases as mc
 import test_ordinal_cpu as oc
-from conftest import assert_parity
+from oracle import lik_ordinal
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ["elbo", "g_m_u", "g_L_u", "g_variance", "g_lengthscale", "g_W", "g_kappa", "g_Z"]
 EDGES = {2: [0.3], 3: [-0.8, 0.45], 5: [-2.0, -0.9, 0.1, 1.7], 11: [-4.0, -3.1, -2.5, -1.2, -0.9, 0.0, 0.4, 1.5, 2.6, 2.9]}
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
 
 
 def _gpu_var_exp(y, m, v, **kw):
@@ -47,7 +41,7 @@ def test_var_exp_on_the_high_precision_grid():
 def test_var_exp_matches_restatement(K, N):
     """Bulk-range rows (m in [-3, 3] sigma, v in [1e-3, 4] sigma^2, bins of 0.3 ... 1.6 sigma).  Kernel and restatement each sit
     within their own bulk constant of the true value, so the two constants add (the rule of likgrid.c_kernel_vs_float64); the
-    condition scale S of these rows is the restatement's float64 one (ordinal_ref.var_exp_scale)."""
+    condition scale S of these rows is the restatement's float64 one (lik_ordinal.var_exp_scale)."""
     C = np.array(oc.c_kernel()[oc.BULK]) + np.array(oc.C_ORACLE[oc.BULK])
     for sigma in (0.3, 1.0, 4.0):
         rng = np.random.RandomState(K * 1009 + N + int(10 * sigma))
@@ -57,8 +51,8 @@ def test_var_exp_matches_restatement(K, N):
         got = _gpu_var_exp(y, m, v, bin_edges=e, sigma=sigma)
         assert got[0].shape == (N,) and got[1].shape == (N, 1) and got[2].shape == (N, 1)
         got = likgrid.pack(*got, N)
-        want = likgrid.pack(*ordinal_ref.var_exp(y, m, v, bin_edges=e, sigma=sigma), N)
-        r = np.abs(got - want) / (likgrid.EPS * ordinal_ref.var_exp_scale(y, m, v, bin_edges=e, sigma=sigma))
+        want = likgrid.pack(*lik_ordinal.var_exp(y, m, v, bin_edges=e, sigma=sigma), N)
+        r = np.abs(got - want) / (likgrid.EPS * lik_ordinal.var_exp_scale(y, m, v, bin_edges=e, sigma=sigma))
         assert np.all(np.isfinite(got)) and np.all(r <= C[None, :]), (K, N, sigma, r.max(0))
     from hetmogp_amd import Ordinal
     lik = Ordinal(bin_edges=e, sigma=sigma)
@@ -110,7 +104,7 @@ def test_sample_class_frequencies():
         y = sample("Ordinal", F[:, None], seed=100 + K, bin_edges=e, sigma=sigma)[:, 0]
         assert y.shape == (N,) and np.array_equal(y, np.round(y)) and y.min() >= 1 and y.max() <= K
         Fp = F if f is None else F[:1]                                  # (in slices: no N x K x several temporaries at once)
-        P = np.concatenate([ordinal_ref.class_probs(Fp[i:i + 100000], np.zeros(len(Fp[i:i + 100000])), bin_edges=e, sigma=sigma)
+        P = np.concatenate([lik_ordinal.class_probs(Fp[i:i + 100000], np.zeros(len(Fp[i:i + 100000])), bin_edges=e, sigma=sigma)
                             for i in range(0, len(Fp), 100000)])
         p, se = P.mean(0), np.sqrt((P * (1.0 - P)).mean(0) / N)
         assert np.all(N * p >= 1000.0)                                  # the normal bound applies to every class
@@ -131,17 +125,17 @@ def test_log_predictive():
         m = rng.uniform(-40.0, 40.0, N) * sigma                       # far tails included: un-clipped log p
         y0 = y
         got = log_predictive_rows("Ordinal", y, m, np.zeros(N), num_samples=128, seed=4, bin_edges=e, sigma=sigma)
-        want = ordinal_ref.logpdf(y, m, bin_edges=e, sigma=sigma)     # v = 0: every sample is f = m
+        want = lik_ordinal.logpdf(y, m, bin_edges=e, sigma=sigma)     # v = 0: every sample is f = m
         assert np.all(np.isfinite(got)) and np.max(np.abs(got - want) / np.maximum(1.0, np.abs(want))) < 1e-10, (K, sigma)
         # v > 0: within 5 Monte-Carlo standard errors (from the restatement's own samples) of the closed form log P_y(m, v)
         # (labels drawn from the closed-form probabilities, so that the estimator's own distribution is not a rare-event one)
         m2, v2 = rng.uniform(-2.5, 2.5, N) * sigma, 10.0 ** rng.uniform(-2.0, 0.0, N) * sigma ** 2
-        cum = np.cumsum(ordinal_ref.class_probs(m2, v2, bin_edges=e, sigma=sigma), 1)
+        cum = np.cumsum(lik_ordinal.class_probs(m2, v2, bin_edges=e, sigma=sigma), 1)
         y = np.minimum(1 + (rng.rand(N, 1) > cum).sum(1), K).astype(float)
         S = 16384
         got = log_predictive_rows("Ordinal", y, m2, v2, num_samples=S, seed=9, bin_edges=e, sigma=sigma)
-        closed = ordinal_ref.log_prob(y, m2, v2, bin_edges=e, sigma=sigma)
-        _, se = ordinal_ref.log_predictive_rows(y, m2, v2, S, np.random.RandomState(1), bin_edges=e, sigma=sigma)
+        closed = lik_ordinal.log_prob(y, m2, v2, bin_edges=e, sigma=sigma)
+        _, se = lik_ordinal.log_predictive_rows(y, m2, v2, S, np.random.RandomState(1), bin_edges=e, sigma=sigma)
         assert np.all(np.abs(got - closed) <= 5.0 * se + 1e-12), (K, sigma, np.max(np.abs(got - closed) / se))
     from hetmogp_amd import Ordinal
     lp = Ordinal(bin_edges=e, sigma=sigma).log_predictive(y0[:, None], m[:, None], np.zeros((N, 1)), 64, seed=1)
@@ -200,95 +194,27 @@ SET_OCG = [ORD11, ("Categorical", {"K": 3}), ("Gaussian", {"sigma": 0.7})]
 SET_OO = [ORD3, ORD5]
 
 
-def _case(seed, specs, Ns, M, Q, P):
-    """Seeded case built by the engine suite's generator (Ordinal tasks drawn as Bernoulli -- same dim_f --, then their observations
-    replaced by labels in 1..K)."""
-    from oracle import svmogp_oracle as so
-    from test_gpu_engine import synth
-    proxy = [("Bernoulli", {}) if n == "Ordinal" else (n, kw) for n, kw in specs]
-    prm, _, X, Y = synth(seed, proxy, Ns, M, Q, P, tuple(0.9 + 0.15 * q for q in range(Q)))
-    rng = np.random.RandomState(seed + 1)
-    for t, (n, kw) in enumerate(specs):
-        if n == "Ordinal":
-            Y[t] = rng.randint(1, kw["K"] + 1, (Ns[t], 1)).astype(float)
-    return prm, so.make_problem(specs, Q, M, P), X, Y
-
-
-def _engine(prob, X, Y, **kw):
-    from hetmogp_amd.engine import Engine
-    e = Engine(prob["specs"], prob["Q"], prob["M"], prob["P"], **kw)
-    e.set_data(X, Y)
-    return e
-
-
-def _run(e, prm, bs=None, **kw):
-    args = dict(Z=prm["Z"], m_u=prm["m_u"], L_flat=prm["L_flat"], variance=prm["variance"], lengthscale=prm["lengthscale"],
-                W=prm["W"], kappa=prm["kappa"], batch_scale=bs)
-    args.update(kw)
-    return e.elbo_grad(**args)
-
-
 CASES = [(SET_O, 16, 1, 1), (SET_GOB, 16, 3, 1), (SET_OCG, 100, 3, 1), (SET_GOB, 100, 1, 2), (SET_O, 128, 3, 2),
          (SET_OCG, 128, 1, 1), (SET_GOB, 256, 3, 1), (SET_OO, 256, 2, 1)]
 
 
 @pytest.mark.parametrize("specs,M,Q,P", CASES, ids=["%s-M%d-Q%d-P%d" % ("+".join(n for n, _ in c[0]), c[1], c[2], c[3])
                                                      for c in CASES])
-def test_elbo_grad_vs_oracle(monkeypatch, specs, M, Q, P):
-    from oracle import svmogp_oracle as so
-    ordinal_ref.install(monkeypatch)
+def test_elbo_grad_vs_oracle(specs, M, Q, P):
     Ns = [300, 257, 129][:len(specs)]
-    prm, prob, X, Y = _case(1900 + M + 7 * Q + P, specs, Ns, M, Q, P)
-    want = so.elbo_grad_fused(prm, prob, X, Y)
-    e1, e2 = _engine(prob, X, Y), _engine(prob, X, Y, chunk_rows=97)          # one row pool / several
-    for e in (e1, e2):
-        out = _run(e, prm)
-        for k in KEYS:
-            assert_parity(out[k], want[k], k)
-    # a minibatch: row ranges of every task with batch scales N / n
-    rb = [n // 5 for n in Ns]
-    re = [min(n, b + max(1, n // 3)) for n, b in zip(Ns, rb)]
-    bs = [float(n) / (e_ - b) for n, b, e_ in zip(Ns, rb, re)]
-    wantb = so.elbo_grad_fused(prm, prob, [x[b:e_] for x, b, e_ in zip(X, rb, re)], [y[b:e_] for y, b, e_ in zip(Y, rb, re)],
-                               batch_scale=bs)
-    outb = _run(e2, prm, bs, row_begin=rb, row_end=re)
-    for k in KEYS:
-        assert_parity(outb[k], wantb[k], "minibatch " + k)
-    e1.close(), e2.close()
+    mc.check_vs_oracle(mc.family_case(1900 + M + 7 * Q + P, specs, Ns, M, Q, P), Ns)
 
 
 @pytest.mark.parametrize("specs", [SET_GOB, SET_OO], ids=["Gaussian+Ordinal+Bernoulli", "two-Ordinal-segments"])
-def test_small_model_path_carries_ordinal(monkeypatch, specs):
-    """M <= 64: the fused small-model kernels (their hipGraph is the witness: only that path captures one) launch the same
-    quadrature, all segments in one quad_multi_kernel pass; the second set is two Ordinal segments with different tables."""
-    from oracle import svmogp_oracle as so
-    ordinal_ref.install(monkeypatch)
-    prm, prob, X, Y = _case(177, specs, [300, 257, 129][:len(specs)], 48, 2, 1)
-    want = so.elbo_grad_fused(prm, prob, X, Y)
-    es, er = _engine(prob, X, Y), _engine(prob, X, Y, small_path=False)
-    for _ in range(3):
-        a, b = _run(es, prm), _run(er, prm)
-    assert es.graph_stats()[0] >= 1 and er.graph_stats() == (0, 0), (es.graph_stats(), er.graph_stats())
-    worst = {k: rel(a[k], b[k]) for k in KEYS}
-    print("small vs regular path, relative difference per array:", {k: "%.1e" % x for k, x in worst.items()})
-    assert worst["elbo"] < 1e-12, worst
-    for k in KEYS:
-        assert worst[k] < 1e-10, (k, worst[k])
-        assert_parity(a[k], want[k], k)
-    es.close(), er.close()
+def test_small_model_path_carries_ordinal(specs):
+    """All segments in one quad_multi_kernel pass; the second set is two Ordinal segments with different tables."""
+    n = len(specs)
+    Ns = [300, 257, 129][:n]
+    mc.check_small_vs_regular(mc.family_case(177, specs, Ns, 48, 2, 1), Ns, ([60, 50, 20][:n], [160, 137, 129][:n]))
 
 
-def test_strict_qf_with_ordinal_vs_literal_oracle(monkeypatch):
-    from oracle import svmogp_oracle as so
-    ordinal_ref.install(monkeypatch)
-    prm, prob, X, Y = _case(131, SET_OCG, [400, 300, 257], 128, 2, 1)
-    lit = so.elbo_grad_literal(prm, prob, X, Y)
-    e = _engine(prob, X, Y, strict_qf=True)
-    out = _run(e, prm)
-    assert out["rungs"] == [-1, -1]
-    for k in KEYS:
-        assert_parity(out[k], lit[k], k)
-    e.close()
+def test_strict_qf_with_ordinal_vs_literal_oracle():
+    mc.check_strict_vs_literal(mc.family_case(131, SET_OCG, [400, 300, 257], 128, 2, 1))
 
 
 # ------------------------------------------------------------------------------------------------ facade end to end

@@ -9,15 +9,10 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import GOLDEN, rel_norm as rel
 
 pytestmark = pytest.mark.gpu
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "mpred_*.npz")))
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
 
 
 def build(g):

@@ -12,15 +12,11 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, assert_parity
+from conftest import GOLDEN, assert_parity, rel_norm as rel
+from model_cases import synth
 
 pytestmark = pytest.mark.gpu
 KEYS = ["elbo", "KL", "g_m_u", "g_L_u", "g_variance", "g_lengthscale", "g_W", "g_kappa", "g_Z"]
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
 
 
 def _pair(prob, X, Y):
@@ -74,16 +70,11 @@ def test_small_path_equals_regular_path(name):
     es.close(), er.close()
 
 
-def _synth(seed, specs, Ns, M, Q, P, cs):
-    from test_gpu_engine import synth
-    return synth(seed, specs, Ns, M, Q, P, cs)
-
-
 @pytest.mark.parametrize("M,Q,P", [(64, 4, 1), (64, 2, 2), (33, 3, 3), (1, 1, 1), (65, 2, 1)])
 def test_small_sizes_vs_oracle_and_regular(M, Q, P):
     from oracle import svmogp_oracle as so
     specs = [("Gaussian", {"sigma": 0.5}), ("Poisson", {}), ("Beta", {}), ("Categorical", {"K": 3})]
-    prm, prob, X, Y = _synth(700 + M + P, specs, [300, 257, 129, 200], M, Q, P, (0.9, 1.1, 1.3, 1.0)[:Q])
+    prm, prob, X, Y = synth(700 + M + P, specs, [300, 257, 129, 200], M, Q, P, (0.9, 1.1, 1.3, 1.0)[:Q])
     want = so.elbo_grad_fused(prm, prob, X, Y)
     es, er = _pair(prob, X, Y)
     a, b = es.elbo_grad(**_args(prm)), er.elbo_grad(**_args(prm))
@@ -99,7 +90,7 @@ def test_small_sizes_vs_oracle_and_regular(M, Q, P):
 def test_jitter_ladder_falls_back_to_the_regular_path():
     from oracle import svmogp_oracle as so
     specs = [("Gaussian", {"sigma": 0.5}), ("Bernoulli", {})]
-    prm, prob, X, Y = _synth(13, specs, [300, 200], 24, 2, 1, (4.0, 5.0))
+    prm, prob, X, Y = synth(13, specs, [300, 200], 24, 2, 1, (4.0, 5.0))
     prm["Z"] = np.tile(np.linspace(0, 1, 24)[:, None], (1, 2))
     want = so.elbo_grad_fused(prm, prob, X, Y)
     assert min(want["rungs"]) >= 0
@@ -217,7 +208,7 @@ def test_quadrature_launch_variants_agree():
     # (a) 9 tasks -> per-segment launches on the small path
     specs9 = [("Gaussian", {"sigma": 0.4 + 0.05 * i}) if i % 3 == 0 else (("Bernoulli", {}) if i % 3 == 1 else ("Poisson", {}))
               for i in range(9)]
-    prm, prob, X, Y = _synth(911, specs9, [60 + 7 * i for i in range(9)], 24, 2, 1, (1.0, 1.2))
+    prm, prob, X, Y = synth(911, specs9, [60 + 7 * i for i in range(9)], 24, 2, 1, (1.0, 1.2))
     es, er = _pair(prob, X, Y)
     a, b = es.elbo_grad(**_args(prm)), er.elbo_grad(**_args(prm))
     for k in KEYS:
@@ -225,7 +216,7 @@ def test_quadrature_launch_variants_agree():
     es.close(), er.close()
     # (b) a wave-per-row likelihood with more than 2048 quadrature blocks (9000 rows x 64 lanes / 256) beside a thread-per-row one
     specs = [("Categorical", {"K": 3}), ("Gaussian", {"sigma": 0.5})]
-    prm, prob, X, Y = _synth(912, specs, [9000, 500], 32, 2, 1, (1.0, 1.2))
+    prm, prob, X, Y = synth(912, specs, [9000, 500], 32, 2, 1, (1.0, 1.2))
     es, er = _pair(prob, X, Y)
     a, b = es.elbo_grad(**_args(prm)), er.elbo_grad(**_args(prm))
     for k in KEYS:
@@ -245,7 +236,7 @@ def test_replayed_graph_detects_a_failed_factorisation():
     page-locked block) -- also when a three-call evaluation, whose info words travel by their own early copy, ran in between --
     and the evaluation must be repeated on the regular path: same rung and same numbers as the regular engine."""
     specs = [("Gaussian", {"sigma": 0.5}), ("Bernoulli", {})]
-    prm, prob, X, Y = _synth(13, specs, [300, 200], 24, 2, 1, (4.0, 5.0))
+    prm, prob, X, Y = synth(13, specs, [300, 200], 24, 2, 1, (4.0, 5.0))
     bad = dict(prm)
     bad["Z"] = np.tile(np.linspace(0, 1, 24)[:, None], (1, 2))      # (the ladder case of the test above)
     good = dict(prm)

@@ -1,24 +1,18 @@
 """GPU: the heteroscedastic Student-t likelihood through every layer -- the building blocks (var_exp, predictive,
-sample, log_predictive) against the NumPy restatement in tests/student_ref.py and against closed forms, the refusal of an invalid
-deg_free, the whole ELBO + gradient against the unchanged oracle (its likelihood dispatch monkeypatched to the restatement for
-"Student"), the small-model and strict q(f) paths, and the model facade end to end, including the robustness the family is for."""
+sample, log_predictive) against the NumPy restatement in oracle/lik_student.py and against closed forms, the refusal of an invalid
+deg_free, the whole ELBO + gradient against the oracle (the checks of tests/model_cases.py) on the default, several-pool, minibatch,
+small-model and strict q(f) paths, and the model facade end to end, including the robustness the family is for."""
 import warnings
 
 import numpy as np
 import pytest
 from scipy import stats
 
-import student_ref
-from conftest import assert_parity, elementwise_excess
+import model_cases as mc
+from conftest import elementwise_excess
+from oracle import lik_student
 
 pytestmark = pytest.mark.gpu
-
-KEYS = ["elbo", "g_m_u", "g_L_u", "g_variance", "g_lengthscale", "g_W", "g_kappa", "g_Z"]
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300))
 
 
 def _rows(rng, N, r_max=50.0):
@@ -40,7 +34,7 @@ def test_var_exp_matches_numpy_tensor_rule(nu, N):
     if N == 1:
         m[0, 0] = y[0] - 37.0                         # the single row is an outlier
     ve, dm, dv = var_exp("Student", y, m, v, deg_free=nu)
-    want = student_ref.var_exp(y, m, v, deg_free=nu)
+    want = lik_student.var_exp(y, m, v, deg_free=nu)
     for name, a, b in zip(("ve", "dm", "dv"), (ve, dm, dv), want):
         ex = elementwise_excess(a, b, rtol=1e-12, floor=1e-14)
         assert ex <= 1.0, (name, nu, N, ex)
@@ -75,7 +69,7 @@ def test_predictive_closed_form_and_missing_moments():
     v = 10.0 ** rng.uniform(-6.0, 0.5, (N, 2))
     for nu in (2.5, 5.0, 30.0):
         mean, var = predictive("Student", m, v, deg_free=nu)
-        wm, wv = student_ref.predictive(m, v, deg_free=nu)
+        wm, wv = lik_student.predictive(m, v, deg_free=nu)
         assert mean.shape == (N, 1) and var.shape == (N, 1)
         assert np.max(np.abs(mean - wm) / np.abs(wm)) <= 1e-13 and np.max(np.abs(var - wv) / wv) <= 1e-13, nu
     mean, var = predictive("Student", m, v, deg_free=2.0)             # 1 < nu <= 2: mean exists, variance does not
@@ -121,10 +115,10 @@ def test_log_predictive_at_vanishing_variance():
     v = np.zeros_like(m)
     for nu in (1.0, 5.0, 30.0):
         got = log_predictive_rows("Student", y, m, v, num_samples=256, seed=4, deg_free=nu)
-        want = student_ref.logpdf_and_derivatives(y, m[:, 0], m[:, 1], nu)[0]
+        want = lik_student.logpdf_and_derivatives(y, m[:, 0], m[:, 1], nu)[0]
         assert np.max(np.abs(got - want) / np.maximum(1.0, np.abs(want))) < 1e-10, nu
     lp = Student(None, 5.0).log_predictive(y[:, None], m, v, 64, seed=1)
-    want = student_ref.logpdf_and_derivatives(y, m[:, 0], m[:, 1], 5.0)[0].sum() / 64.0
+    want = lik_student.logpdf_and_derivatives(y, m[:, 0], m[:, 1], 5.0)[0].sum() / 64.0
     assert abs(lp - want) < 1e-10 * abs(want)
 
 
@@ -149,95 +143,24 @@ SET_GSB = [("Gaussian", {"sigma": 0.5}), ("Student", {"deg_free": 3.0}), ("Berno
 SET_SCH = [("Student", {"deg_free": 2.5}), ("Categorical", {"K": 3}), ("HetGaussian", {})]
 
 
-def _case(seed, specs, Ns, M, Q, P):
-    """Seeded case built by the engine suite's generator (Student tasks drawn as HetGaussian -- same dim_f --, then their
-    observations replaced by heavy-tailed ones with 5 % gross outliers)."""
-    from oracle import svmogp_oracle as so
-    from test_gpu_engine import synth
-    proxy = [("HetGaussian", {}) if n == "Student" else (n, kw) for n, kw in specs]
-    prm, _, X, Y = synth(seed, proxy, Ns, M, Q, P, tuple(0.9 + 0.15 * q for q in range(Q)))
-    rng = np.random.RandomState(seed + 1)
-    for t, (n, kw) in enumerate(specs):
-        if n == "Student":
-            y = 0.5 * rng.standard_t(kw["deg_free"], (Ns[t], 1))
-            out = rng.rand(Ns[t], 1) < 0.05
-            Y[t] = np.where(out, y + 20.0 * np.sign(rng.randn(Ns[t], 1)), y)
-    return prm, so.make_problem(specs, Q, M, P), X, Y
-
-
-def _engine(prob, X, Y, **kw):
-    from hetmogp_amd.engine import Engine
-    e = Engine(prob["specs"], prob["Q"], prob["M"], prob["P"], **kw)
-    e.set_data(X, Y)
-    return e
-
-
-def _run(e, prm, bs=None, **kw):
-    args = dict(Z=prm["Z"], m_u=prm["m_u"], L_flat=prm["L_flat"], variance=prm["variance"], lengthscale=prm["lengthscale"],
-                W=prm["W"], kappa=prm["kappa"], batch_scale=bs)
-    args.update(kw)
-    return e.elbo_grad(**args)
-
-
 CASES = [(SET_S, 16, 1, 1), (SET_GSB, 16, 3, 1), (SET_SCH, 100, 3, 1), (SET_GSB, 100, 1, 2), (SET_S, 128, 3, 2),
          (SET_SCH, 128, 1, 1), (SET_GSB, 256, 3, 1), (SET_SCH, 256, 1, 2)]
 
 
 @pytest.mark.parametrize("specs,M,Q,P", CASES, ids=["%s-M%d-Q%d-P%d" % ("+".join(n for n, _ in c[0]), c[1], c[2], c[3])
                                                      for c in CASES])
-def test_elbo_grad_vs_oracle(monkeypatch, specs, M, Q, P):
-    from oracle import svmogp_oracle as so
-    student_ref.install(monkeypatch)
+def test_elbo_grad_vs_oracle(specs, M, Q, P):
     Ns = [300, 257, 129][:len(specs)]
-    prm, prob, X, Y = _case(900 + M + 7 * Q + P, specs, Ns, M, Q, P)
-    want = so.elbo_grad_fused(prm, prob, X, Y)
-    e1, e2 = _engine(prob, X, Y), _engine(prob, X, Y, chunk_rows=97)          # one row pool / several
-    for e in (e1, e2):
-        out = _run(e, prm)
-        for k in KEYS:
-            assert rel(out[k], want[k]) < 1e-8, (k, rel(out[k], want[k]))
-    # a minibatch: row ranges of every task with batch scales N / n
-    rb = [n // 5 for n in Ns]
-    re = [min(n, b + max(1, n // 3)) for n, b in zip(Ns, rb)]
-    bs = [float(n) / (e_ - b) for n, b, e_ in zip(Ns, rb, re)]
-    wantb = so.elbo_grad_fused(prm, prob, [x[b:e_] for x, b, e_ in zip(X, rb, re)], [y[b:e_] for y, b, e_ in zip(Y, rb, re)],
-                               batch_scale=bs)
-    outb = _run(e2, prm, bs, row_begin=rb, row_end=re)
-    for k in KEYS:
-        assert rel(outb[k], wantb[k]) < 1e-8, ("minibatch", k, rel(outb[k], wantb[k]))
-    e1.close(), e2.close()
+    mc.check_vs_oracle(mc.family_case(900 + M + 7 * Q + P, specs, Ns, M, Q, P), Ns)
 
 
-def test_small_model_path_carries_student(monkeypatch):
-    """M <= 64: the fused small-model kernels (their hipGraph is the witness: only that path captures one) equal the regular path."""
-    from oracle import svmogp_oracle as so
-    student_ref.install(monkeypatch)
-    prm, prob, X, Y = _case(77, SET_GSB, [300, 257, 129], 48, 2, 1)
-    want = so.elbo_grad_fused(prm, prob, X, Y)
-    es, er = _engine(prob, X, Y), _engine(prob, X, Y, small_path=False)
-    for _ in range(3):
-        a, b = _run(es, prm), _run(er, prm)
-    assert es.graph_stats()[0] >= 1 and er.graph_stats() == (0, 0), (es.graph_stats(), er.graph_stats())
-    worst = {k: rel(a[k], b[k]) for k in KEYS}
-    print("small vs regular path, relative difference per array:", {k: "%.1e" % x for k, x in worst.items()})
-    assert worst["elbo"] < 1e-12, worst
-    for k in KEYS:
-        assert worst[k] < 1e-10, (k, worst[k])
-        assert rel(a[k], want[k]) < 1e-8, (k, rel(a[k], want[k]))
-    es.close(), er.close()
+def test_small_model_path_carries_student():
+    Ns = [300, 257, 129]
+    mc.check_small_vs_regular(mc.family_case(77, SET_GSB, Ns, 48, 2, 1), Ns, ([60, 50, 20], [160, 137, 129]))
 
 
-def test_strict_qf_with_student_vs_literal_oracle(monkeypatch):
-    from oracle import svmogp_oracle as so
-    student_ref.install(monkeypatch)
-    prm, prob, X, Y = _case(31, SET_SCH, [400, 300, 257], 128, 2, 1)
-    lit = so.elbo_grad_literal(prm, prob, X, Y)
-    e = _engine(prob, X, Y, strict_qf=True)
-    out = _run(e, prm)
-    assert out["rungs"] == [-1, -1]
-    for k in KEYS:
-        assert_parity(out[k], lit[k], k)
-    e.close()
+def test_strict_qf_with_student_vs_literal_oracle():
+    mc.check_strict_vs_literal(mc.family_case(31, SET_SCH, [400, 300, 257], 128, 2, 1))
 
 
 # ------------------------------------------------------------------------------------------------ facade end to end

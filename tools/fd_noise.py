@@ -3,7 +3,7 @@ import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
-from test_gpu_engine import make_engine, run, synth
+from model_cases import make_engine, run, synth
 specs = [("HetGaussian", {}), ("Categorical", {"K": 4}), ("Poisson", {}), ("Exponential", {})]
 prm, prob, X, Y = synth(40 + len("eight_2d"), specs, [90, 80, 70, 60], 25, 3, 2, (1.0, 1.2, 0.9))
 prm["kappa"] = 0.05 + 0.02 * np.arange(prob["Q"] * prob["Df"], dtype=float).reshape(prob["Q"], prob["Df"])

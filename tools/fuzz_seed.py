@@ -5,7 +5,8 @@ if os.environ.get("FUZZ_PKG_ROOT"):          # an older build of the package (A/
     sys.path.insert(0, os.environ["FUZZ_PKG_ROOT"])
 import numpy as np
 import test_gpu_fuzz as fz
-from test_gpu_engine import KEYS, make_engine, rel, run, synth
+from conftest import rel_norm as rel
+from model_cases import KEYS, make_engine, run, synth
 from oracle import svmogp_oracle as so
 seed = int(sys.argv[1])
 rng = np.random.RandomState(1000 + seed)

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from conftest import elementwise_excess, rel_norm     # noqa: E402
-from test_gpu_engine import KEYS, synth               # noqa: E402
+from model_cases import KEYS, synth               # noqa: E402
 from hetmogp_amd.engine import Engine                 # noqa: E402
 from oracle import svmogp_oracle as so                # noqa: E402
 

@@ -121,6 +121,11 @@ EXPORTS = {
     "hmogp_potrs_rows": (C.c_int, [C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int64, c_double_p]),
     "hmogp_gemm_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_double_p,
                                  C.c_int32, c_double_p, C.c_int32, C.c_double, c_double_p, C.c_int32]),
+    "hmogp_var_exp_dparam": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hmogp_lik_param_count": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p]),
+    "hmogp_set_lik_params": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
+    "hmogp_lik_grad_enable": (C.c_int, [C.c_void_p, C.c_int32]),
+    "hmogp_lik_grad_read": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
     "hmogp_ordinal_table": (C.c_int, [C.c_int32, c_double_p, C.c_double, c_double_p]),
     "hmogp_predictive": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, c_double_p, c_double_p, c_double_p,
                                    c_double_p]),

@@ -105,7 +105,11 @@ int hmogp_set_task_data(hmogp_handle h, int32_t t, const double* X, const double
 
 int hmogp_step_begin(hmogp_handle h, const hmogp_params* p) {
   if (!h) return HMOGP_E_INVALID;
-  return guarded(h, [&] { h->begin(p); });
+  return guarded(h, [&] {
+    if (h->lik_grad_on)   // (the bundle and the wire format carry no likelihood-parameter gradient: out of scope)
+      throw EngineError{HMOGP_E_INVALID, "hmogp_step_begin: the split step does not carry the likelihood-parameter gradient (hmogp_lik_grad_enable is on)"};
+    h->begin(p);
+  });
 }
 
 int hmogp_stats_buffer(hmogp_handle h, void** device_ptr, int64_t* count) {
@@ -252,6 +256,8 @@ int hmogp_elbo_grad(hmogp_handle h, const hmogp_params* p, hmogp_outputs* out) {
 int hmogp_elbo_grad_sharded(hmogp_handle h, const hmogp_params* p, hmogp_outputs* out) {
   if (!h) return HMOGP_E_INVALID;
   return guarded(h, [&] {
+    if (h->lik_grad_on)
+      throw EngineError{HMOGP_E_INVALID, "hmogp_elbo_grad_sharded: the sharded step does not carry the likelihood-parameter gradient (hmogp_lik_grad_enable is on)"};
     if (!h->comm) throw EngineError{HMOGP_E_STATE, "hmogp_elbo_grad_sharded without a communicator (hmogp_comm_init)"};
     try {
       h->begin(p, false, true);
@@ -465,6 +471,44 @@ int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t 
     HIP_TRY(hipMemcpy(dm, ddm.p, sizeof(double) * N * J, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(dv, ddv.p, sizeof(double) * N * J, hipMemcpyDeviceToHost));
   });
+}
+
+int hmogp_var_exp_dparam(int32_t device, int32_t lik_id, double lik_param, int64_t N, const double* y, const double* m,
+                         const double* v, double* out) {
+  return guarded(nullptr, [&] {
+    need_device(device);
+    if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
+    const int J = lik_dimf(lik_id, lik_param);
+    check_lik_param(lik_id, lik_param);
+    const int Cn = lik_dparam_cols(lik_id);
+    if (Cn == 0) throw EngineError{HMOGP_E_INVALID, "hmogp_var_exp_dparam: this likelihood has no parameters of its own"};
+    if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !y || !m || !v || !out) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
+    DevBuf dy, dmm, dvv, dout;
+    upload_y(lik_id, lik_param, y, N, dy);
+    dmm.ensure(sizeof(double) * N * J), dvv.ensure(sizeof(double) * N * J), dout.ensure(sizeof(double) * N * Cn);
+    HIP_TRY(hipMemcpy(dmm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dvv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
+    launch_var_exp_dparam(lik_id, lik_param, N, dy.d(), dmm.d(), dvv.d(), dout.d(), nullptr);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout.p, sizeof(double) * N * Cn, hipMemcpyDeviceToHost));
+  });
+}
+
+int hmogp_lik_param_count(hmogp_handle h, int32_t t, int32_t* n) {
+  if (!h || !n) return HMOGP_E_INVALID;
+  return guarded(h, [&] { *n = h->lik_param_count(t); });
+}
+int hmogp_set_lik_params(hmogp_handle h, int32_t t, const double* values, int32_t n) {
+  if (!h) return HMOGP_E_INVALID;
+  return guarded(h, [&] { h->set_lik_params(t, values, n); });
+}
+int hmogp_lik_grad_enable(hmogp_handle h, int32_t on) {
+  if (!h) return HMOGP_E_INVALID;
+  return guarded(h, [&] { h->lik_grad_enable(on != 0); });
+}
+int hmogp_lik_grad_read(hmogp_handle h, int32_t t, double* g, int32_t n) {
+  if (!h) return HMOGP_E_INVALID;
+  return guarded(h, [&] { h->lik_grad_read(t, g, n); });
 }
 
 int hmogp_ordinal_table(int32_t K, const double* edges, double sigma, double* lik_param_out) {

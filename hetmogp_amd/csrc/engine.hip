@@ -201,7 +201,7 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
   std::vector<double> cuts;
   if (k.lik == HMOGP_LIK_ORDINAL && N > 0) {  // the rows' own cut points depend on the data only; a label that is not an integer in
     cuts.resize(2 * (size_t)N);               // 1..K is refused before the task's state changes
-    ordinal_row_cuts(ordinal_table(k.param), Y, N, cuts.data(), cuts.data() + N);
+    ordinal_row_cuts(task_table(k), Y, N, cuts.data(), cuts.data() + N);
   }
   if (k.lik == HMOGP_LIK_DIRICHLET && N > 0) {   // Y is [N, K]; checked, and its logarithm laid out [K][N], before the state changes
     cuts.resize((size_t)k.dimf * N);
@@ -250,6 +250,7 @@ void hmogp_engine::ensure_workspace(long long rows) {
     winrow.ensure(sizeof(int) * 2 * tiles * Q), wincol.ensure(sizeof(int) * 2 * ncb * Q), winhit.ensure(tiles * ncb);
   }
   ws_rows = rows;
+  ensure_lik_grad_workspace();
 }
 
 void hmogp_engine::ensure_strict_workspace() {

@@ -110,7 +110,29 @@ struct Task {
   int dimy() const { return lik == HMOGP_LIK_DIRICHLET ? dimf : 1; }          // columns of the task's Y
   DevBuf offsets;  // device: quad scalar slot -> bundle offset
   int nscal = 0;
+  // Ordinal, after hmogp_set_lik_params: the task's PRIVATE table replaces the registry entry `param` names
+  bool own_table = false;
+  OrdinalTable table;
 };
+inline const OrdinalTable& task_table(const Task& k) { return k.own_table ? k.table : ordinal_table(k.param); }
+
+// ---- likelihood parameters (lik_param.hip) ----
+// one segment of the gradient kernel: what the quadrature of the same rows reads, plus the labels of an Ordinal task
+struct LikGradArgs {
+  int lik = 0, Q = 1, Df = 0, d0 = 0, nout = 1;
+  double lik_param = 0.0;          // sigma (Gaussian, Ordinal), nu (Student)
+  long long N = 0, off = 0, ldn = 0;
+  const double *y = nullptr, *yaux = nullptr, *label = nullptr;   // [N], offset to the segment's first row
+  const double *p = nullptr, *c = nullptr;                        // [Q][ldn] row statistics of the pool
+  const double *Wd = nullptr, *kapd = nullptr, *vard = nullptr;   // device-resident [Q][Df], [Q][Df], [Q]
+  double* partials = nullptr;                                     // [blocks][nout]
+};
+int lik_dparam_cols(int lik);   // columns of hmogp_var_exp_dparam's output (0: the family has no parameters)
+// y: [N], Ordinal [2][N] (lower, upper cut points); m, v: [N][dim_f]; out: [N][lik_dparam_cols]; Ordinal: `param` is the table id
+void launch_var_exp_dparam(int lik, double param, long long N, const double* y, const double* m, const double* v, double* out,
+                           hipStream_t s);
+// dst[0 .. nout) += (scaled ? *scaled : scale) * sum over the segment's rows, block partials summed in a fixed order
+void launch_lik_grad(const LikGradArgs& a, double* dst, double scale, const double* scaled, hipStream_t s);
 
 int lik_dimf(int lik, double param);
 void check_lik_param(int lik, double param);  // HMOGP_E_INVALID for a parameter the likelihood has no value for (Student: nu;
@@ -509,4 +531,15 @@ struct hmogp_engine {
   int qu_natgrad_status();
 
   void predict_f(const double* Xnew, long long Nnew, double* m, double* v);
+
+  // ---- likelihood parameters (lik_param.hip) ----
+  bool lik_grad_on = false;      // hmogp_lik_grad_enable: persistent
+  bool lik_grad_valid = false;   // an evaluation has run since the switch was turned on
+  DevBuf likpart, dlikgrad;      // block partials of one segment | [T][HMOGP_ORDINAL_MAXK] gradients of the last evaluation
+  int lik_param_count(int t) const;
+  void set_lik_params(int t, const double* values, int n);
+  void lik_grad_enable(bool on);
+  void ensure_lik_grad_workspace();
+  void lik_grad_pool(const std::vector<Seg>& pl);   // behind the quadrature of one pool, on the evaluation's stream
+  void lik_grad_read(int t, double* g, int n);
 };

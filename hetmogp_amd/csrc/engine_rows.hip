@@ -387,6 +387,10 @@ void hmogp_engine::row_pass() {
   // (pools: see plan_pools())
   const long long ldn = ws_rows;
   if (!kuf_prefetched) HIP_TRY(hipMemsetAsync(stats.p, 0, sizeof(double) * nstats, st));   // (else: with the prefetch)
+  if (lik_grad_on) {
+    HIP_TRY(hipMemsetAsync(dlikgrad.p, 0, sizeof(double) * (size_t)T * HMOGP_ORDINAL_MAXK, st));
+    lik_grad_valid = true;
+  }
   const int tiles = (M + 127) / 128;
   const long long wtiles = (ws_rows + 127) / 128;
   const long long sK = ldn * M;                           // per-latent stride of the K^ / P~ workspaces
@@ -572,6 +576,8 @@ void hmogp_engine::row_pass() {
       Scope sc(this, CAT_QUAD, 2 * (int)pl.size());
       for (auto& sg : pl) quad_segment(sg);
     }
+    // likelihood parameters: d ve / d theta of the rows whose quadrature just ran, from the same p / c
+    if (lik_grad_on && (group_mask & HMOGP_GROUP_HYPER)) lik_grad_pool(pl);
     // The column statistics (HBM-bound: K^ and P~ streamed once) run on the second stream BESIDE the weighted Gram: both
     // only need the row weights of the quadrature and write disjoint parts of the bundle.  (Measured alternative: the
     // column statistics of segment i beside the forward contraction of segment i + 1 -- the Gram gains 4.0 ms, the

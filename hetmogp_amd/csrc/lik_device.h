@@ -6,6 +6,8 @@
 // including its clips and quirks:
 //   Q1  Gamma / Beta: Gauss-Hermite weights divided by sqrt(pi) twice (gamma.py:110,139-141; beta.py:113,142-144)
 //   Q2  Categorical: d/dm is the constant onehot(y)[d] - 1 (categorical.py:102-113)
+// At the end of the file: the derivatives with respect to the likelihoods' OWN parameters (Gaussian sigma, Student nu, Ordinal cut
+// points and sigma), appended so that nothing above them changes.
 // Lane mapping: closed forms, 1-D quadratures and Gamma (separable in its two functions) use ONE lane per row;
 // Beta (100 nodes), Student (400 nodes), Categorical (10^(K-1) nodes) and Dirichlet (10^K nodes) use ONE WAVE per row, nodes strided over the
 // 64 lanes and reduced with wavefront shuffles.
@@ -1148,4 +1150,111 @@ __device__ __forceinline__ void lik_eval(double y, double yaux, const double* m,
 #pragma unroll
     for (int j = 0; j < 2; ++j) o.gm[j] *= M_PI, o.gv[j] *= M_PI;
   }
+}
+
+// ============================================================================ derivatives with respect to the likelihoods' own parameters
+// DESIGN 9e.  What a Gaussian (sigma), a Student (nu) and an Ordinal (its cut points and sigma) likelihood can learn: the derivative of
+// the row's variational expectation -- of exactly the finite rule above -- with respect to that parameter.  Nothing above this line
+// changes: the quadrature kernels keep their code and registers.
+
+// Gaussian: ve = -log(2 pi)/2 - log sigma - ((y - m)^2 + v) / (2 sigma^2)
+__device__ __forceinline__ double lik_gaussian_dsigma(double y, double m, double v, double sigma) {
+  const double r = y - m;
+  return -1.0 / sigma + (r * r + v) / (sigma * sigma * sigma);
+}
+
+// C'(nu) of the Student constant C(nu) = lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2:
+//   C'(nu) = psi((nu+1)/2)/2 - psi(nu/2)/2 - 1/(2 nu)
+// is O(nu^-2) while its terms are O(log nu): from nu = 64 on it is the derivative of student_logc's series in x = nu/2 (two more
+// terms than student_logc keeps: the truncation error has to stay below the rounding of a result that is itself ~1e-4),
+//   dC/dx = 1/(8x^2) - 1/(64x^4) + 1/(128x^6) - 17/(2048x^8) + 31/(2048x^10) - 691/(16384x^12),    C'(nu) = dC/dx / 2.
+__device__ __forceinline__ double student_dlogc(double nu) {
+  if (nu < 64.0) return 0.5 * digamma_pos(0.5 * (nu + 1.0)) - 0.5 * digamma_pos(0.5 * nu) - 0.5 / nu;
+  const double ix = 2.0 / nu, z = ix * ix;
+  return 0.5 * z *
+         (1.0 / 8.0 + z * (-1.0 / 64.0 + z * (1.0 / 128.0 + z * (-17.0 / 2048.0 + z * (31.0 / 2048.0 + z * (-691.0 / 16384.0))))));
+}
+
+// Student, 20 x 20 rule, one wave per row, nodes strided over the lanes as in lik_student_wave (same node tables in the wave's LDS slice):
+//   d ve / d nu = C'(nu) + sum_ij w_i w_j [ -log1p(u)/2 + (nu+1)/(2 nu) u/(1+u) ],     u = r^2 s / nu
+__device__ __forceinline__ double lik_student_dnu_wave(double y, const double* m, const double* v, double nu, int lane, double* tab) {
+  if (lane < 40) {
+    const int dim = lane / 20, i = lane - 20 * dim;
+    const double f = GH20_X[i] * sqrt(2.0 * v[dim]) + m[dim];
+    if (dim == 0)
+      tab[i] = y - f;
+    else
+      tab[40 + i] = safe_exp(-f);
+  }
+  __builtin_amdgcn_wave_barrier();  // written and read by this wave only (LDS operations of a wave are in order)
+  const double rnu = 1.0 / nu, kn = 0.5 * (nu + 1.0) * rnu;
+  double acc = 0.0;
+  for (int n = lane; n < 400; n += 64) {
+    const int i = n / 20, j = n - 20 * i;
+    const double w = GH20_WN[i] * GH20_WN[j];
+    const double r = tab[i], s = tab[40 + j];
+    const double u = r * r * s * rnu;
+    acc += w * (kn * (u / (1.0 + u)) - 0.5 * log1p(u));
+  }
+  return student_dlogc(nu) + wave_sum(acc);
+}
+
+// Ordinal: the sibling of ordinal_node for the parameters.  With P = Phi(b) - Phi(a) it returns qa = phi(a) / P, qb = phi(b) / P and
+// h = (a phi(a) - b phi(b)) / P, from which
+//   d lp / d lo = -qa / sigma,    d lp / d hi = qb / sigma,    d lp / d sigma = h / sigma.
+// Same three branches as ordinal_node (the mirror step swaps the two ratios; h is even under it):
+//   branch             qa                               qb
+//   P = 1 - Q          phi(a) / (1 - Q)                 phi(b) / (1 - Q)
+//   erfcx              sqrt(2/pi) exp(-d) / D           sqrt(2/pi) / D
+// exp(-d) = 1 + expm1(-d) is evaluated as an exponential of its own: beyond d = 37 the sum 1 + expm1(-d) is 0 in float64, while
+// d/d lo of a bin far from f IS exp(-d) times a number of order 1 and has nothing to hide a lost factor behind (h has: its -b).
+// An infinite cut contributes 0 (phi = 0; exp(-d) = 0).
+__device__ __forceinline__ void ordinal_node_dparam(double a, double b, double& qa, double& qb, double& h) {
+  bool mir = false;
+  if (a + b > 0.0) {
+    const double t = a;
+    a = -b, b = -t, mir = true;
+  }
+  double ra, rb;
+  bool done = false;
+  if (b > 0.0) {
+    const double Q = 0.5 * (erfc(-a * M_SQRT1_2) + erfc(b * M_SQRT1_2));
+    if (Q < 0.5) {
+      const double rP = 1.0 / (1.0 - Q);
+      const double pa = ORD_INV_SQRT_2PI * exp(-0.5 * a * a), pb = ORD_INV_SQRT_2PI * exp(-0.5 * b * b);
+      ra = pa * rP, rb = pb * rP;
+      h = ((isinf(a) ? 0.0 : a * pa) - (isinf(b) ? 0.0 : b * pb)) * rP;
+      done = true;
+    }
+  }
+  if (!done) {
+    const double Ea = erfcx(-a * M_SQRT1_2), Eb = erfcx(-b * M_SQRT1_2);  // a = -inf: E = 0
+    const double x = 0.5 * (b - a) * (a + b);                              // -d
+    const double em = expm1(x), ed = exp(x);                               // a = -inf: expm1 = -1, exp = 0
+    const double D = (Eb - Ea) - em * Ea;
+    const double rD = ORD_SQRT_2_OVER_PI / D;
+    ra = ed * rD, rb = rD;
+    h = ((isinf(a) ? 0.0 : a * ed) - b) * rD;
+  }
+  qa = mir ? rb : ra;
+  qb = mir ? ra : rb;
+}
+
+// 20-node rule, one lane per row: the derivatives of lik_ordinal's ve with respect to the row's own two cut points and to sigma
+__device__ __forceinline__ void lik_ordinal_dparam(double lo, double hi, double m, double v, double sigma, double& dlo, double& dhi,
+                                                   double& dsig) {
+  const double s = sqrt(2.0 * v);
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma unroll 1
+  for (int i = 0; i < 20; ++i) {
+    const double f = GH20_X[i] * s + m, w = GH20_WN[i];
+    double qa, qb, h;
+    ordinal_node_dparam((lo - f) / sigma, (hi - f) / sigma, qa, qb, h);
+    a0 += qa * w;
+    a1 += qb * w;
+    a2 += h * w;
+  }
+  dlo = -a0 / sigma;
+  dhi = a1 / sigma;
+  dsig = a2 / sigma;
 }

@@ -418,6 +418,31 @@ class Engine(object):
             out["dL_dKdiag"].append(b)
         return out
 
+    # ------------------------------------------------------------------------------------------ likelihood parameters
+    def lik_param_count(self, t):
+        """Parameters task t's likelihood can learn: 1 (Gaussian sigma, Student deg_free), K (Ordinal: K - 1 cuts, then sigma), else 0."""
+        cache = self.__dict__.setdefault("_lik_counts", {})      # (fixed at construction: K does not change)
+        if t not in cache:
+            n = C.c_int32(0)
+            check(lib.hmogp_lik_param_count(self._h, int(t), C.byref(n)), self._h)
+            cache[t] = int(n.value)
+        return cache[t]
+
+    def set_lik_params(self, t, values):
+        """New values of task t's likelihood parameters (layout of `lik_param_count`); InvalidArgument leaves the task unchanged."""
+        values = _f64(values).reshape(-1)
+        check(lib.hmogp_set_lik_params(self._h, int(t), _p(values), values.shape[0]), self._h)
+
+    def lik_grad_enable(self, on=True):
+        """Persistent switch: evaluations whose group_mask holds GROUP_HYPER also compute d ELBO / d (likelihood parameters)."""
+        check(lib.hmogp_lik_grad_enable(self._h, 1 if on else 0), self._h)
+
+    def lik_grad(self, t):
+        """d ELBO / d theta of task t from the last evaluation (zeros when gated or switched off)."""
+        g = np.zeros(self.lik_param_count(t))
+        check(lib.hmogp_lik_grad_read(self._h, int(t), _p(g), g.shape[0]), self._h)
+        return g
+
     def graph_stats(self):
         """(graphs captured, evaluations replayed) of the small-model hipGraph mechanism (hmogp_graph_stats)."""
         cap, rep = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
@@ -530,6 +555,19 @@ def var_exp(name, y, m, v, device=None, quirks="reference", **kw):
     check(lib.hmogp_var_exp_ex(device, LIK_IDS[name], lik_param(name, **kw), _lib.quirk_mask(quirks), y.shape[0], _p(y),
                                _p(m), _p(v), _p(ve), _p(dm), _p(dv)))
     return ve, dm, dv
+
+
+def var_exp_dparam(name, y, m, v, device=None, **kw):
+    """Per-row derivatives of the variational expectation with respect to the likelihood's own parameters: (N, 1) for Gaussian
+    (d sigma) and Student (d deg_free), (N, 3) for Ordinal (d lo, d hi, d sigma of the row's own two cut points)."""
+    device = _resolve_device(device)
+    y, m, v = _y_rows(name, y, **kw), _f64(m), _f64(v)
+    J = lik_dim_f(name, **kw)
+    m, v = m.reshape(-1, J), v.reshape(-1, J)
+    cols = dict(Gaussian=1, Student=1, Ordinal=3).get(name, 1)
+    out = np.zeros((y.shape[0], cols))
+    check(lib.hmogp_var_exp_dparam(device, LIK_IDS[name], lik_param(name, **kw), y.shape[0], _p(y), _p(m), _p(v), _p(out)))
+    return out
 
 
 def predictive(name, m, v, gh_T=0, device=None, **kw):

@@ -4,6 +4,8 @@ expectations themselves are HIP kernels (csrc/lik_device.h).  `var_exp` / `var_e
 reference's signatures and run on the device."""
 import numpy as np
 
+from .param import Param
+
 
 class _Lik(object):
     name = None
@@ -11,6 +13,18 @@ class _Lik(object):
 
     def kwargs(self):
         return {}
+
+    # ---- the likelihood's own parameters (DESIGN 9e): nothing to learn unless a constructor flag asks for it
+    def learnable_params(self):
+        """[(name, Param)] of the parameters this likelihood learns; SVMOGP lists them as `likelihood.<t>.<name>`."""
+        return []
+
+    def engine_values(self):
+        """Current values in the layout of `hmogp_set_lik_params` (None: the engine's constants stay what they are)."""
+        return None
+
+    def set_engine_gradient(self, g):
+        """Writes the Params' `.gradient` from the engine's raw gradient (layout of `engine_values`)."""
 
     def get_metadata(self):
         """(dim_y, dim_f, dim_p) as the reference's get_metadata()."""
@@ -60,11 +74,34 @@ class _Lik(object):
 class Gaussian(_Lik):
     name = "Gaussian"
 
-    def __init__(self, sigma=None, gp_link=None):
-        self.sigma = 0.5 if sigma is None else sigma       # gaussian.py:21-24
+    def __init__(self, sigma=None, gp_link=None, learn_sigma=False):
+        self._sigma = 0.5 if sigma is None else sigma      # gaussian.py:21-24
+        self._p_sigma = Param("sigma", [float(self._sigma)], positive=True) if learn_sigma else None
+
+    @property
+    def sigma(self):
+        """The current value: a plain float also while it is being learned."""
+        return self._sigma if self._p_sigma is None else float(self._p_sigma.values[0])
+
+    @sigma.setter
+    def sigma(self, value):
+        if self._p_sigma is None:
+            self._sigma = value
+        else:
+            self._p_sigma[...] = float(value)
 
     def kwargs(self):
         return {"sigma": self.sigma}
+
+    def learnable_params(self):
+        return [] if self._p_sigma is None else [("sigma", self._p_sigma)]
+
+    def engine_values(self):
+        return None if self._p_sigma is None else np.array([self.sigma])
+
+    def set_engine_gradient(self, g):
+        if self._p_sigma is not None:
+            self._p_sigma.gradient = [g[0]]
 
 
 class Bernoulli(_Lik):
@@ -114,30 +151,116 @@ class Beta(_Lik):
 
 class Student(_Lik):
     """Heteroscedastic Student-t (the reference's likelihoods/student.py is a constructor only; the model is DESIGN 9):
-    f0 = location (identity link), f1 = log of the squared scale (HetGaussian's convention), deg_free = nu fixed.
-    `gp_link` comes first so that the reference's positional call Student(gp_link) still works."""
+    f0 = location (identity link), f1 = log of the squared scale (HetGaussian's convention), deg_free = nu -- fixed, or learned
+    with `learn_deg_free=True`.  `gp_link` comes first so that the reference's positional call Student(gp_link) still works."""
     name = "Student"
     _dims = (1, 2, 1)
 
-    def __init__(self, gp_link=None, deg_free=5.0):
-        self.deg_free = float(deg_free)                    # 5: GPy's StudentT default
+    def __init__(self, gp_link=None, deg_free=5.0, learn_deg_free=False):
+        self._deg_free = float(deg_free)                   # 5: GPy's StudentT default
+        self._p_nu = Param("deg_free", [self._deg_free], positive=True) if learn_deg_free else None
+
+    @property
+    def deg_free(self):
+        return self._deg_free if self._p_nu is None else float(self._p_nu.values[0])
+
+    @deg_free.setter
+    def deg_free(self, value):
+        if self._p_nu is None:
+            self._deg_free = float(value)
+        else:
+            self._p_nu[...] = float(value)
 
     def kwargs(self):
         return {"deg_free": self.deg_free}
 
+    def learnable_params(self):
+        return [] if self._p_nu is None else [("deg_free", self._p_nu)]
+
+    def engine_values(self):
+        return None if self._p_nu is None else np.array([self.deg_free])
+
+    def set_engine_gradient(self, g):
+        if self._p_nu is not None:
+            self._p_nu.gradient = [g[0]]
+
 
 class Ordinal(_Lik):
     """Ordered probit (the reference's likelihoods/ordinal.py is a constructor only; the model is DESIGN 9b): one latent function,
-    labels 1..K, p(y = k | f) = Phi((b_k - f) / sigma) - Phi((b_{k-1} - f) / sigma) with fixed cut points b_1 < ... < b_{K-1}
-    (`bin_edges`; K alone: b_k = k - K/2) and fixed sigma.  `gp_link` comes first so that the reference's positional call
-    Ordinal(gp_link) still works.  `predictive` returns the mean and variance of the label, (N, 1) each."""
+    labels 1..K, p(y = k | f) = Phi((b_k - f) / sigma) - Phi((b_{k-1} - f) / sigma) with cut points b_1 < ... < b_{K-1}
+    (`bin_edges`; K alone: b_k = k - K/2) and noise scale sigma -- fixed, or learned with `learn_edges` / `learn_sigma`:
+    the cuts are then the free `edge0` = b_1 and the positive `gaps` delta_k = b_{k+1} - b_k, which no optimiser can make cross.
+    `gp_link` comes first so that the reference's positional call Ordinal(gp_link) still works.  `predictive` returns the mean and
+    variance of the label, (N, 1) each.
+    The stand-alone helpers (`predictive`, `samples`, `log_predictive`, `var_exp`) carry the cuts through `hmogp_ordinal_table`, whose
+    process-wide registry keeps every DISTINCT table (at most 4096, then InvalidArgument): calling one of them after every update of
+    learned cuts, e.g. to log a score per training iteration, uses one entry per call.  The model's own evaluations do not (the
+    engine keeps a private table); log every so many iterations, or at the end."""
     name = "Ordinal"
 
-    def __init__(self, gp_link=None, K=None, bin_edges=None, sigma=1.0):
+    def __init__(self, gp_link=None, K=None, bin_edges=None, sigma=1.0, learn_edges=False, learn_sigma=False):
         from .engine import ordinal_edges
-        self.bin_edges = ordinal_edges(K, bin_edges)
-        self.K = len(self.bin_edges) + 1
-        self.sigma = float(sigma)
+        self._edges = ordinal_edges(K, bin_edges)
+        self.K = len(self._edges) + 1
+        self._sigma = float(sigma)
+        self._p_edge0 = self._p_gaps = self._p_sigma = None
+        if learn_edges:
+            self._p_edge0 = Param("edge0", self._edges[:1])
+            if self.K > 2:
+                self._p_gaps = Param("gaps", np.diff(self._edges), positive=True)
+        if learn_sigma:
+            self._p_sigma = Param("sigma", [self._sigma], positive=True)
+
+    @property
+    def bin_edges(self):
+        """The current cut points, a plain array."""
+        if self._p_edge0 is None:
+            return self._edges
+        gaps = self._p_gaps.values if self._p_gaps is not None else np.zeros(0)
+        return float(self._p_edge0.values[0]) + np.concatenate([[0.0], np.cumsum(gaps)])
+
+    @bin_edges.setter
+    def bin_edges(self, value):
+        """Assignable as before; the number of cuts (K) is fixed at construction and the values are checked by the library."""
+        e = np.array(value, dtype=np.float64).reshape(-1)
+        if len(e) != self.K - 1:
+            raise ValueError("Ordinal: %d cut points assigned to a likelihood with K = %d" % (len(e), self.K))
+        if self._p_edge0 is None:
+            self._edges = e
+        else:
+            self._p_edge0[...] = e[:1]
+            if self._p_gaps is not None:
+                self._p_gaps[...] = np.diff(e)
+
+    @property
+    def sigma(self):
+        return self._sigma if self._p_sigma is None else float(self._p_sigma.values[0])
+
+    @sigma.setter
+    def sigma(self, value):
+        if self._p_sigma is None:
+            self._sigma = float(value)
+        else:
+            self._p_sigma[...] = float(value)
+
+    def learnable_params(self):
+        return [(p.name, p) for p in (self._p_edge0, self._p_gaps, self._p_sigma) if p is not None]
+
+    def engine_values(self):
+        if self._p_edge0 is None and self._p_sigma is None:
+            return None
+        return np.concatenate([self.bin_edges, [self.sigma]])
+
+    def set_engine_gradient(self, g):
+        """Chain rule from the gradient with respect to the raw cuts: g_{b_1} = sum_k g_k, g_{delta_j} = sum_{k > j} g_k."""
+        g = np.asarray(g, dtype=float)
+        K = self.K
+        if self._p_edge0 is not None:
+            self._p_edge0.gradient = [g[:K - 1].sum()]
+        if self._p_gaps is not None:
+            self._p_gaps.gradient = [g[j + 1:K - 1].sum() for j in range(K - 2)]
+        if self._p_sigma is not None:
+            self._p_sigma.gradient = [g[K - 1]]
 
     def kwargs(self):
         return {"K": self.K, "bin_edges": [float(b) for b in self.bin_edges], "sigma": self.sigma}

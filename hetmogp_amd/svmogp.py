@@ -347,6 +347,12 @@ class SVMOGP(object):
         self.evaluations = 0              # parameters_changed() calls (a repeated evaluation at a switch counts once)
         self.strict_qf = (strict_qf is True) or (not self._strict_auto and bool(strict_qf))
         strict_qf = self.strict_qf
+        # likelihoods that learn their own parameters
+        self._lik_learn = [(t, l) for t, l in enumerate(likelihood.likelihoods_list) if l.learnable_params()]
+        self._lik_pushed = {}
+        if self._lik_learn and distributed:
+            raise NotImplementedError("learnable likelihood parameters in a row-sharded (distributed=True) model: the statistic "
+                                      "bundle does not carry their gradient (DESIGN 9e)")
         self._engine = Engine(likelihood.specs(), self.num_latent_funcs, self.num_inducing, self.Xdim, device=device,
                               chunk_rows=chunk_rows, exact_zero_windows=exact_zero_windows, cache_kuu=True,
                               reuse_outputs=True, quirks=quirks, strict_qf=strict_qf,
@@ -355,6 +361,8 @@ class SVMOGP(object):
         # (distributed: the fused small-model kernels are chosen from THIS rank's row count; ranks whose shares straddle the
         #  threshold would round the replicated M x M algebra differently and the device-resident q(u) replicas, which are never
         #  re-synchronised, would drift apart -- every rank therefore keeps the regular kernels.  ADVICE r4)
+        if self._lik_learn:                       #  turned on once, here, if and only if a likelihood learns something
+            self._engine.lik_grad_enable(True)
         self._engine.set_data(self.Xmulti_all, self.Ymulti_all)
         self._engine_has_full = True      # False while foreign data (set_data of arrays that are not row ranges) is resident
         # distributed=True (inside an initialised torch.distributed group, one process per GPU): the rows of every
@@ -471,10 +479,16 @@ class SVMOGP(object):
                     mask &= ~_lib.GROUP_QU
                 hyper = [k.variance for k in self.kern_list] + [k.lengthscale for k in self.kern_list] + \
                         [B.W for B in self.B_list] + [B.kappa for B in self.B_list]
+                hyper += [p for _, l in self._lik_learn for _, p in l.learnable_params()]
                 if all(h.is_fixed for h in hyper):
                     mask &= ~_lib.GROUP_HYPER
         if self.Z.is_fixed:
             mask &= ~_lib.GROUP_Z
+        for t, l in self._lik_learn:             # values an optimiser moved since the last evaluation go to the engine first
+            vals = l.engine_values()
+            if self._lik_pushed.get(t) is None or not np.array_equal(vals, self._lik_pushed[t]):
+                self._engine.set_lik_params(t, vals)
+                self._lik_pushed[t] = vals.copy()
         W0, k0 = self._construction_W()
         evaluate = self._engine.elbo_grad
         if self._dist is not None:
@@ -524,6 +538,8 @@ class SVMOGP(object):
             B.gradient = np.hstack([out["g_W"][q], out["g_kappa"][q]])
         if not self.Z.is_fixed:
             self.Z.gradient = out["g_Z"]
+        for t, l in self._lik_learn:             # gated with the hyper-parameters (zeros otherwise); read after a strict re-evaluation
+            l.set_engine_gradient(self._engine.lik_grad(t))
         self.posteriors = None                                               # built lazily (prediction only)
         self._dirty = False
 
@@ -665,6 +681,8 @@ class SVMOGP(object):
             out += [("%s.kern_q%d.variance" % (self.name, q), k.variance), ("%s.kern_q%d.lengthscale" % (self.name, q), k.lengthscale)]
         for q, B in enumerate(self.B_list):
             out += [("%s.B_q%d.W" % (self.name, q), B.W), ("%s.B_q%d.kappa" % (self.name, q), B.kappa)]
+        for t, l in getattr(self, "_lik_learn", ()):       # last: the layout of a model without them does not move
+            out += [("likelihood.%d.%s" % (t, n), p) for n, p in l.learnable_params()]
         return out
 
     def __getitem__(self, pattern):

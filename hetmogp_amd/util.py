@@ -138,11 +138,12 @@ _GROUPS = {
     "Z": lambda m: m.Z,
     "m_u": lambda m: m.q_u_means,
     "L_u": lambda m: m.q_u_chols,
+    "likelihood": lambda m: m["likelihood\\..*"],      # the likelihoods' own parameters (none unless a constructor asked: DESIGN 9e)
 }
 VEM_SCHEDULE = (
     # (label, groups frozen in this half-step, groups released in this half-step)
-    ("VE", ("lengthscale", "variance", "Z", "W"), ("m_u", "L_u")),
-    ("VM", ("m_u", "L_u"), ("lengthscale", "variance", "Z", "W")),
+    ("VE", ("lengthscale", "variance", "Z", "W", "likelihood"), ("m_u", "L_u")),
+    ("VM", ("m_u", "L_u"), ("lengthscale", "variance", "Z", "W", "likelihood")),
 )
 
 

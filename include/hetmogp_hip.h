@@ -397,6 +397,33 @@ int hmogp_ordinal_table(int32_t K, const double* edges, double sigma, double* li
 int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t quirks, int64_t N, const double* y,
                      const double* m, const double* v, double* ve, double* dm, double* dv);
 
+/* ---- Likelihood parameters: Gaussian sigma, Student deg_free, Ordinal cut points and sigma can be LEARNED.  All of it is
+ * new symbols: the ABI version, the three structs and the eval_flags mask are unchanged, and an engine that never calls them behaves
+ * as before.
+ *
+ * Per-row derivatives of the variational expectation with respect to the likelihood's own parameters (same rules as hmogp_var_exp:
+ * closed form, GH20, 20 x 20).  y, m, v as for hmogp_var_exp, validated the same way; out is [N, C]:
+ *   Gaussian C = 1: d ve / d sigma;   Student C = 1: d ve / d deg_free (the constant's derivative included);
+ *   Ordinal  C = 3: d ve / d lo, d ve / d hi, d ve / d sigma for the row's OWN two cut points (0 for an infinite one).
+ * Any other family: HMOGP_E_INVALID.                                                                             */
+int hmogp_var_exp_dparam(int32_t device, int32_t lik_id, double lik_param, int64_t N, const double* y, const double* m,
+                         const double* v, double* out);
+/* Number of parameters of task t: 1 (Gaussian: sigma), 1 (Student: deg_free), K (Ordinal: b_1 .. b_{K-1}, then sigma), 0 otherwise. */
+int hmogp_lik_param_count(hmogp_handle h, int32_t t, int32_t* n);
+/* New values for task t's parameters (n = hmogp_lik_param_count), validated like the constructors (sigma, deg_free finite and > 0;
+ * cut points finite and strictly increasing); on HMOGP_E_INVALID the task is unchanged.  An Ordinal task keeps a private table from
+ * here on -- the registry of hmogp_ordinal_table is not touched, any number of updates is fine -- and its rows' cut points are
+ * rebuilt on the device from the resident labels.  Captured small-model graphs are dropped.                       */
+int hmogp_set_lik_params(hmogp_handle h, int32_t t, const double* values, int32_t n);
+/* Persistent switch, default off.  While it is on, every evaluation whose group_mask contains HMOGP_GROUP_HYPER also computes
+ * batch_scale[t] * sum_rows d ve / d theta for every task with parameters (one row kernel per family behind the quadrature,
+ * block partials summed in a fixed order: two evaluations give the same bits).  hmogp_step_begin and hmogp_elbo_grad_sharded
+ * return HMOGP_E_INVALID while it is on: the bundle and the wire format do not carry this gradient.                 */
+int hmogp_lik_grad_enable(hmogp_handle h, int32_t on);
+/* d ELBO / d theta of the last evaluation, layout of hmogp_set_lik_params (Ordinal: with respect to the raw cut points and sigma).
+ * Zeros when the switch is off or the evaluation's group_mask had no HMOGP_GROUP_HYPER.                            */
+int hmogp_lik_grad_read(hmogp_handle h, int32_t t, double* g, int32_t n);
+
 /* Predictive mean / variance of y under q(f) = N(m, diag v): the reference's `<likelihood>.predictive(m, v)`
  * (e.g. bernoulli.py:113-128, gamma.py:196-238, categorical.py:224-269), consumed by HetLikelihood.predictive
  * (het_likelihood.py:133-148).  m, v [N, dim_f] -> mean, var [N, dim_p] (dim_p = K-1 for Categorical, K for Dirichlet, else 1).

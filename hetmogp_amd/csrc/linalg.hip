@@ -516,6 +516,20 @@ void launch_trtri_batched(const double* L, double* Linv, double* tmp, int Q, int
     h.alpha = -1.0;
     h.a_tri = +1;  // X22 is lower triangular
     launch_gemm_f64(h, stream);
+    // One step of refinement in working precision: X21 -= X22 (L21 X11 + L22 X21).  The product with the COMPUTED X22 above has
+    // an error of gamma |X22| |L21 X11|, which |Linv| |L| |Linv| does not bound where X22 (L21 X11) cancels (the factor of an RBF
+    // K_uu at cond 1e7: 290 x 2^-52 of that scale at M >= 320); the residual's own error is gamma (|L21| |X11| + |L22| |X21|),
+    // and |X22| times that IS the componentwise bound (0.2 - 0.3 after the step).
+    // R = T + L22 X21   (r x s) += (r x r)(r x s)
+    GemmArgs rr = h;
+    rr.A = L + (long long)s * M + s;
+    rr.B = Linv + (long long)s * M;
+    rr.C = tmp + (long long)s * M;
+    rr.alpha = 1.0, rr.beta = 1.0;  // (a_tri = +1: L22 is lower triangular)
+    launch_gemm_f64(rr, stream);
+    // X21 -= X22 R
+    h.beta = 1.0;
+    launch_gemm_f64(h, stream);
   }
 }
 

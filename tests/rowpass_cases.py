@@ -64,6 +64,7 @@ def _build(tag):
         gv_max=[float(o["gv"].max()) if o["N"] else -np.inf for o in rows],
         seconds=time.time() - t0)
     out["facts"] = facts
+    out["side"] = side          # the M x M side, for the references of the tail (tests/tail_cases.py)
     return tag, out
 
 
@@ -71,7 +72,7 @@ _REFS = {}
 
 
 def references():
-    """{tag: {"default": (R, S), "facts": {...}[, "bs", "shard", "strict"]}} for every case; built on first use."""
+    """{tag: {"default": (R, S), "facts": {...}, "side": [...][, "bs", "shard", "strict"]}} for every case; built on first use."""
     if not _REFS:
         tags = ["F", "E", "D", "C", "B", "A"]          # the longest first
         n = max(1, min(16, len(tags), os.cpu_count() or 1))

@@ -39,7 +39,7 @@ void need_device(int device) {
 
 // y [N] of a building block -> device.  Ordinal: the labels are checked and replaced by the rows' lower, then upper cut points
 // ([2][N], what launch_var_exp / launch_log_predictive read), so that the device code is the engine's.  Dirichlet: y is [N][K]; it is
-// checked and replaced by log y_k as [K][N], the engine's layout.
+// checked and replaced by log y_k as [K][N], the engine's layout.  Negative Binomial: the counts are checked and uploaded as they are.
 void upload_y(int lik_id, double lik_param, const double* y, long long N, DevBuf& dy) {
   if (lik_id == HMOGP_LIK_DIRICHLET) {
     const int K = (int)lik_param;
@@ -49,6 +49,7 @@ void upload_y(int lik_id, double lik_param, const double* y, long long N, DevBuf
     HIP_TRY(hipMemcpy(dy.p, ly.data(), sizeof(double) * K * N, hipMemcpyHostToDevice));
     return;
   }
+  if (lik_id == HMOGP_LIK_NEGBINOMIAL) negbinomial_check_rows(y, N);
   if (lik_id != HMOGP_LIK_ORDINAL) {
     dy.ensure(sizeof(double) * N);
     HIP_TRY(hipMemcpy(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice));

@@ -207,6 +207,7 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
     cuts.resize((size_t)k.dimf * N);
     dirichlet_log_rows(k.dimf, Y, N, cuts.data());
   }
+  if (k.lik == HMOGP_LIK_NEGBINOMIAL && N > 0) negbinomial_check_rows(Y, N);   // counts, checked before the task's state changes
   k.N = N;
   began = false;
   staged_key.clear();
@@ -216,7 +217,7 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
   k.Y.ensure(sizeof(double) * N * k.dimy());
   HIP_TRY(hipMemcpy(k.X.p, X, sizeof(double) * N * P, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(k.Y.p, Y, sizeof(double) * N * k.dimy(), hipMemcpyHostToDevice));
-  if (k.lik == HMOGP_LIK_POISSON) {  // gammaln(y+1) depends on the data only (poisson.py:33)
+  if (k.lik == HMOGP_LIK_POISSON || k.lik == HMOGP_LIK_NEGBINOMIAL) {  // gammaln(y+1) depends on the data only (poisson.py:33)
     k.Yaux.ensure(sizeof(double) * N);
     launch_gammaln1p(k.Y.d(), k.Yaux.d(), N, st);
     HIP_TRY(hipStreamSynchronize(st));

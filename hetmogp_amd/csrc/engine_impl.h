@@ -140,6 +140,7 @@ void check_lik_param(int lik, double param);  // HMOGP_E_INVALID for a parameter
                                               // 2 .. HMOGP_DIRICHLET_MAXK)
 // Dirichlet: compositions y [N][K] (every y_k finite and > 0, |sum_k y_k - 1| <= 1e-6, else HMOGP_E_INVALID) -> ly [K][N] = log y_k
 void dirichlet_log_rows(int K, const double* y, long long N, double* ly);
+void negbinomial_check_rows(const double* y, long long N);   // HMOGP_E_INVALID unless every y is a finite, non-negative integer
 // Ordinal: labels y [N] (integers in 1..K, else HMOGP_E_INVALID) -> the rows' lower / upper cut points (-inf / +inf at the ends)
 void ordinal_row_cuts(const OrdinalTable& tb, const double* y, long long N, double* lo, double* hi);
 // registers (or finds) a table; returns the value to pass as lik_param

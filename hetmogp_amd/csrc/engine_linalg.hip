@@ -18,7 +18,8 @@ int lik_dimf(int lik, double param) {
     case HMOGP_LIK_HETGAUSSIAN:
     case HMOGP_LIK_GAMMA:
     case HMOGP_LIK_BETA:
-    case HMOGP_LIK_STUDENT: return 2;
+    case HMOGP_LIK_STUDENT:
+    case HMOGP_LIK_NEGBINOMIAL: return 2;
     case HMOGP_LIK_CATEGORICAL: return (int)param - 1;
     case HMOGP_LIK_DIRICHLET: return (param >= 2.0 && param <= (double)HMOGP_DIRICHLET_MAXK) ? (int)param : -1;
     default: return -1;
@@ -31,6 +32,13 @@ void check_lik_param(int lik, double param) {
   if (lik == HMOGP_LIK_ORDINAL) (void)ordinal_table(param);
   if (lik == HMOGP_LIK_DIRICHLET && !(param >= 2.0 && param <= (double)HMOGP_DIRICHLET_MAXK && param == std::floor(param)))
     throw EngineError{HMOGP_E_INVALID, "Dirichlet: K must be an integer in 2 .. HMOGP_DIRICHLET_MAXK"};
+}
+
+// ------------------------------------------------------------------------------------ Negative Binomial rows
+void negbinomial_check_rows(const double* y, long long N) {
+  for (long long n = 0; n < N; ++n)
+    if (!(std::isfinite(y[n]) && y[n] >= 0.0 && y[n] == std::floor(y[n])))
+      throw EngineError{HMOGP_E_INVALID, "NegBinomial: every y must be a finite, non-negative integer"};
 }
 
 // ------------------------------------------------------------------------------------ Dirichlet rows

@@ -2,15 +2,15 @@
 // the mean / variance of q(f), for the eight likelihoods of /root/reference/likelihoods/*.py (SURVEY.md 8a, rows
 // L1-L8), the heteroscedastic Student-t the reference only stubs (student.py; contract: DESIGN 9) and the Ordinal (ordered
 // probit) likelihood it only stubs as well (ordinal.py; contract: DESIGN 9b; no clip), and the Dirichlet likelihood, its third stub
-// (dirichlet.py; contract: DESIGN 9d; K log y_k per row).  Results reproduce the reference's formulas
-// including its clips and quirks:
+// (dirichlet.py; contract: DESIGN 9d; K log y_k per row), and the heteroscedastic Negative Binomial, which the reference does not have
+// (contract: DESIGN 9h).  Results reproduce the reference's formulas including its clips and quirks:
 //   Q1  Gamma / Beta: Gauss-Hermite weights divided by sqrt(pi) twice (gamma.py:110,139-141; beta.py:113,142-144)
 //   Q2  Categorical: d/dm is the constant onehot(y)[d] - 1 (categorical.py:102-113)
 // At the end of the file: the derivatives with respect to the likelihoods' OWN parameters (Gaussian sigma, Student nu, Ordinal cut
 // points and sigma), appended so that nothing above them changes.
 // Lane mapping: closed forms, 1-D quadratures and Gamma (separable in its two functions) use ONE lane per row;
-// Beta (100 nodes), Student (400 nodes), Categorical (10^(K-1) nodes) and Dirichlet (10^K nodes) use ONE WAVE per row, nodes strided over the
-// 64 lanes and reduced with wavefront shuffles.
+// Beta (100 nodes), Student and Negative Binomial (400 nodes), Categorical (10^(K-1) nodes) and Dirichlet (10^K nodes) use ONE WAVE per row,
+// nodes strided over the 64 lanes and reduced with wavefront shuffles.
 #pragma once
 #include "common.h"
 #include "gh_tables.h"
@@ -227,7 +227,8 @@ __device__ __forceinline__ void lik_ordinal_predictive(const OrdinalTable& tb, d
 // Per-wave LDS scratch of the tensor-rule likelihoods (doubles): Categorical [0,80) exp(f_k(node i)), [80,160) f_k(node i),
 // [160,170) normalised GH weights; Beta [0,80) a_i, psi(a_i), zeta(2,a_i), lgamma(a_i) and the same four for b_j;
 // Student [0,60) r_i = y - f0(node i), f1(node j), s_j = exp(-f1(node j)); Dirichlet [0,40) a_k(node i), [40,50) weights,
-// [56,64) m_k, v_k (predictive, T = 20: [0,80) a_k(node i), [80,88) m_k, v_k).
+// [56,64) m_k, v_k (predictive, T = 20: [0,80) a_k(node i), [80,88) m_k, v_k); Negative Binomial [0,20) min(f0(node i), LIM_VAL), then
+// per node j of f1: [20,40) log r_j, [40,60) r_j, [60,80) G_j - lgamma(y+1), [80,100) r_j D1_j, [100,120) r_j^2 D2_j.
 #define HMOGP_ETAB 176
 
 __device__ __forceinline__ double wave_min(double v) {
@@ -434,6 +435,120 @@ __device__ __forceinline__ void lik_student_wave(double y, const double* m, cons
     h0 += w * (kn * s * (u - 1.0) * a * a);
     g1 += w * (hn * ua - 0.5);
     h1 += w * (-hn * ua * a);
+  }
+  o.ve = wave_sum(ve);
+  o.gm[0] = wave_sum(g0);
+  o.gm[1] = wave_sum(g1);
+  o.gv[0] = 0.5 * wave_sum(h0);
+  o.gv[1] = 0.5 * wave_sum(h1);
+}
+
+// ------------------------------------------------------------------------------------------- Negative Binomial, 20 x 20
+// Heteroscedastic Negative Binomial (no counterpart in the reference): counts y = 0, 1, 2, ..; f0 = log of the mean,
+// f1 = log of the dispersion ("size") r = clip(safe_exp(f1), 1e-9, 1e9) (Gamma's link and clip), Var[y | f] = mu + mu^2 / r.
+// With lr = log r, z = min(f0, LIM_VAL) - lr, sp = softplus(z), p = sigmoid(z), q = 1 - p (mu and p never formed from exp(f0)):
+//   log p  = G - lgamma(y+1) + y z - (r + y) sp             G  = lgamma(y+r) - lgamma(r)
+//   d/df0  = y q - r p                                      D1 = psi(y+r)    - psi(r)
+//   d2/df0 = -(r + y) p q                                   D2 = psi'(y+r)   - psi'(r)
+//   d/df1  = r (D1 - sp) - d/df0
+//   d2/df1 = r (D1 - sp) + r^2 D2 + 2 r p - (r + y) p q     (the clip is ignored in the derivatives, as for Gamma / Beta)
+// G, D1, D2 are never the difference of two large numbers (at r = 1e9, y = 50 the plain difference of lgamma loses 4e-6 of 1e3):
+//   y <= 32             the exact products / sums over k < y:  G = log prod (r + k),  D1 = sum 1/(r + k),  D2 = -sum 1/(r + k)^2
+//                       (at most 32 factors <= 1e9 + 31: the product stays below 1e289 and carries <= 32 roundings)
+//   y > 32, r >= 16     Stirling's series of the two arguments subtracted term by term, the leading terms in closed form:
+//                         G  = y log(r+y) - y + (r - 1/2) log1p(y/r) + [c(r+y) - c(r)]       c(x) = 1/(12x) - 1/(360x^3) + ..
+//                         D1 = log1p(y/r) + y / (2 r (r+y)) + [d(r) - d(r+y)]                d(x) = 1/(12x^2) - 1/(120x^4) + ..
+//                         D2 = -y / (r (r+y)) - y (2r+y) / (2 r^2 (r+y)^2) - [e(r) - e(r+y)] e(x) = 1/(6x^3) - 1/(30x^5) + ..
+//                       (every term of D1 is positive, of D2 negative; truncation at x = 16: c 1.1e-16, d 2.4e-20, e 2.4e-20)
+//   y > 32, r < 16      the plain differences: lgamma(r), psi(r), psi'(r) are small beside their partners or dominate them.
+__device__ __forceinline__ double nb_stirling_c(double x) {  // lgamma(x) - [(x - 1/2) log x - x + log(2 pi)/2], x >= 16
+  const double ix = 1.0 / x, z = ix * ix;
+  return ix * (1.0 / 12.0 + z * (-1.0 / 360.0 + z * (1.0 / 1260.0 + z * (-1.0 / 1680.0 + z * (1.0 / 1188.0)))));
+}
+__device__ __forceinline__ double nb_stirling_d(double x) {  // log x - 1/(2x) - psi(x), x >= 16
+  const double ix = 1.0 / x, z = ix * ix;
+  return z * (1.0 / 12.0 +
+              z * (-1.0 / 120.0 + z * (1.0 / 252.0 + z * (-1.0 / 240.0 + z * (1.0 / 132.0 + z * (-691.0 / 32760.0 + z * (1.0 / 12.0)))))));
+}
+__device__ __forceinline__ double nb_stirling_e(double x) {  // psi'(x) - 1/x - 1/(2x^2), x >= 16
+  const double ix = 1.0 / x, z = ix * ix;
+  return ix * z *
+         (1.0 / 6.0 + z * (-1.0 / 30.0 + z * (1.0 / 42.0 + z * (-1.0 / 30.0 + z * (5.0 / 66.0 + z * (-691.0 / 2730.0 + z * (7.0 / 6.0)))))));
+}
+// y: a non-negative integer-valued double (checked on the host), r in [1e-9, 1e9]
+__device__ __forceinline__ void nb_gamma_diffs(double y, double r, double& G, double& D1, double& D2) {
+  if (y <= 32.0) {
+    const int ny = (int)y;
+    double prod = 1.0, s1 = 0.0, s2 = 0.0;
+    for (int k = 0; k < ny; ++k) {
+      const double t = r + (double)k, it = 1.0 / t;
+      prod *= t;
+      s1 += it;
+      s2 = fma(it, it, s2);
+    }
+    G = log(prod), D1 = s1, D2 = -s2;
+  } else if (r >= 16.0) {
+    const double ry = r + y, l1 = log1p(y / r), rry = r * ry;
+    G = y * log(ry) - y + (r - 0.5) * l1 + (nb_stirling_c(ry) - nb_stirling_c(r));
+    D1 = l1 + y / (2.0 * rry) + (nb_stirling_d(r) - nb_stirling_d(ry));
+    D2 = -y / rry - y * (2.0 * r + y) / (2.0 * rry * rry) - (nb_stirling_e(r) - nb_stirling_e(ry));
+  } else {
+    G = lgamma(y + r) - lgamma(r);
+    D1 = digamma_pos(y + r) - digamma_pos(r);
+    D2 = trigamma_pos(y + r) - trigamma_pos(r);
+  }
+}
+__device__ __forceinline__ double nb_lgamma_diff(double y, double r) {
+  double G, D1, D2;
+  nb_gamma_diffs(y, r, G, D1, D2);
+  return G;
+}
+
+// The full log p at one f (Monte-Carlo log predictive); lgy1 = lgamma(y + 1)
+__device__ __forceinline__ double lik_negbinomial_logpdf(double y, double lgy1, const double* f) {
+  const double r = clip(safe_exp(f[1]), 1e-9, 1e9);
+  const double z = fmin(f[0], LIM_VAL) - log(r);
+  const double sp = fmax(z, 0.0) + log1p(exp(-fabs(z)));
+  return nb_lgamma_diff(y, r) - lgy1 + y * z - (r + y) * sp;
+}
+
+// 20 x 20 Gauss-Hermite tensor rule, weights w/sqrt(pi) once per dimension (Student's convention).  Lanes 0-19 write min(f0(node i), LIM_VAL)
+// into the wave's LDS slice, lanes 20-39 what depends on f1(node j) alone: lr_j, r_j, G_j - lgamma(y+1), r_j D1_j, r_j^2 D2_j (y is
+// the same in the whole wave: the y <= 32 loop does not diverge).  Each of the 400 nodes then costs one exp, one log1p and one reciprocal.
+__device__ __forceinline__ void lik_negbinomial_wave(double y, double lgy1, const double* m, const double* v, int lane, double* tab,
+                                                     LikOut& o) {
+  static_assert(120 <= HMOGP_ETAB, "Negative Binomial table");
+  if (lane < 40) {
+    const int dim = lane / 20, i = lane - 20 * dim;
+    const double f = GH20_X[i] * sqrt(2.0 * v[dim]) + m[dim];
+    if (dim == 0) {
+      tab[i] = fmin(f, LIM_VAL);
+    } else {
+      const double r = clip(safe_exp(f), 1e-9, 1e9);
+      double G, D1, D2;
+      nb_gamma_diffs(y, r, G, D1, D2);
+      tab[20 + i] = log(r);
+      tab[40 + i] = r;
+      tab[60 + i] = G - lgy1;
+      tab[80 + i] = r * D1;
+      tab[100 + i] = r * r * D2;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();  // written and read by this wave only (LDS operations of a wave are in order)
+  double ve = 0.0, g0 = 0.0, g1 = 0.0, h0 = 0.0, h1 = 0.0;
+  for (int n = lane; n < 400; n += 64) {
+    const int i = n / 20, j = n - 20 * i;
+    const double w = GH20_WN[i] * GH20_WN[j];
+    const double r = tab[40 + j], z = tab[i] - tab[20 + j];
+    const double a = exp(-fabs(z)), inv = 1.0 / (1.0 + a), ai = a * inv;
+    const double sp = fmax(z, 0.0) + log1p(a);
+    const double p = z >= 0.0 ? inv : ai, q = z >= 0.0 ? ai : inv;
+    const double rp = r * p, d0 = y * q - rp, ppq = (r + y) * p * q, c = tab[80 + j] - r * sp;
+    ve += w * (tab[60 + j] + y * z - (r + y) * sp);
+    g0 += w * d0;
+    h0 -= w * ppq;
+    g1 += w * (c - d0);
+    h1 += w * (c + tab[100 + j] + 2.0 * rp - ppq);
   }
   o.ve = wave_sum(ve);
   o.gm[0] = wave_sum(g0);
@@ -785,6 +900,10 @@ __device__ __forceinline__ void lik_predictive(const double* m, const double* v,
   } else if (LIK == HMOGP_LIK_STUDENT) {  // closed form: the moments do not exist for nu <= 1 / nu <= 2
     mean[0] = param > 1.0 ? m[0] : nan("");
     var[0] = param > 2.0 ? v[0] + param / (param - 2.0) * safe_exp(m[1] + 0.5 * v[1]) : INFINITY;
+  } else if (LIK == HMOGP_LIK_NEGBINOMIAL) {  // closed form: q(f0), q(f1) independent; no clip, overflow is +inf
+    const double mu = exp(m[0] + 0.5 * v[0]);
+    mean[0] = mu;
+    var[0] = mu + exp(2.0 * m[0] + 2.0 * v[0] - m[1] + 0.5 * v[1]) + (v[0] > 0.0 ? expm1(v[0]) * exp(2.0 * m[0] + v[0]) : 0.0);
   } else {  // Categorical, categorical.py:84-99,224-269: E[rho_d], rho normalised over the K-1 columns; variance zeros
     const int D = (int)param - 1;
     for (int e = lane; e < D * 10; e += 64) {
@@ -944,6 +1063,8 @@ __device__ __forceinline__ double lik_logpdf_sample(double y, double yaux, const
     double lp, g, h;
     ordinal_node((y - f[0]) / param, (yaux - f[0]) / param, lp, g, h);
     return lp;
+  } else if (LIK == HMOGP_LIK_NEGBINOMIAL) {  // yaux = lgamma(y + 1)
+    return lik_negbinomial_logpdf(y, yaux, f);
   }
   return nan("");
 }
@@ -1046,6 +1167,9 @@ __device__ __forceinline__ double lik_sample(RowRng& g, const double* f, double 
   } else if (LIK == HMOGP_LIK_STUDENT) {  // location + scale * t(nu):  z / sqrt(chi2_nu / nu),  chi2_nu = 2 Gamma(nu/2, 1)
     const double z = g.normal(), G = g.gamma(0.5 * param);
     return f[0] + safe_exp(0.5 * f[1]) * z * sqrt(param / (2.0 * G));
+  } else if (LIK == HMOGP_LIK_NEGBINOMIAL) {  // Gamma-Poisson mixture: lambda = mu Gamma(r, 1) / r, y ~ Poisson(lambda)
+    const double r = clip(safe_exp(f[1]), 1e-9, 1e9);
+    return g.poisson(safe_exp(f[0]) * g.gamma(r) / r);
   } else {  // Categorical: labels 1..K, probabilities clipped then renormalised (categorical.py:66-71)
     const int K = (int)param, D = K - 1;
     double e[HMOGP_MAXJ], esum = 0.0;
@@ -1119,7 +1243,10 @@ __host__ __device__ constexpr int lik_pred_lanes(int lik) {
 
 // lanes per row of a likelihood
 __host__ __device__ constexpr int lik_lanes(int lik) {
-  return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_STUDENT || lik == HMOGP_LIK_DIRICHLET) ? 64 : 1;
+  return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_STUDENT || lik == HMOGP_LIK_DIRICHLET ||
+          lik == HMOGP_LIK_NEGBINOMIAL)
+             ? 64
+             : 1;
 }
 
 // Dispatch.  For 64-lane likelihoods every lane of the wave must call with the same row; the result is valid in
@@ -1143,6 +1270,8 @@ __device__ __forceinline__ void lik_eval(double y, double yaux, const double* m,
     lik_student_wave(y, m, v, param, lane, etab, o);
   else if (LIK == HMOGP_LIK_ORDINAL)
     lik_ordinal(y, yaux, m[0], v[0], param, o);   // y / yaux: the row's lower / upper cut point, param: sigma
+  else if (LIK == HMOGP_LIK_NEGBINOMIAL)
+    lik_negbinomial_wave(y, yaux, m, v, lane, etab, o);   // yaux: lgamma(y + 1)
   else
     lik_categorical_t<(CATD > 0 ? CATD : 1)>(y, m, v, lane, etab, quirks, o);
   if ((LIK == HMOGP_LIK_GAMMA || LIK == HMOGP_LIK_BETA) && !(quirks & HMOGP_QUIRK_GAMMA_BETA_PI)) {

@@ -14,7 +14,7 @@ from ._lib import lib, check
 LIK_IDS = dict(Gaussian=_lib.LIK_GAUSSIAN, Bernoulli=_lib.LIK_BERNOULLI, HetGaussian=_lib.LIK_HETGAUSSIAN,
                Categorical=_lib.LIK_CATEGORICAL, Poisson=_lib.LIK_POISSON, Exponential=_lib.LIK_EXPONENTIAL,
                Gamma=_lib.LIK_GAMMA, Beta=_lib.LIK_BETA, Student=_lib.LIK_STUDENT, Ordinal=_lib.LIK_ORDINAL,
-               Dirichlet=_lib.LIK_DIRICHLET)
+               Dirichlet=_lib.LIK_DIRICHLET, NegBinomial=_lib.LIK_NEGBINOMIAL)
 
 
 def _f64(a):
@@ -31,7 +31,8 @@ def lik_dim_f(name, **kw):
         return int(kw["K"]) - 1
     if name == "Dirichlet":
         return int(kw["K"])
-    return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1)[name]
+    return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1,
+                NegBinomial=2)[name]
 
 
 def lik_dim_y(name, **kw):

@@ -292,6 +292,19 @@ class Dirichlet(_Lik):
         return True
 
 
+class NegBinomial(_Lik):
+    """Heteroscedastic Negative Binomial for over-dispersed counts (not in the reference; the model is DESIGN 9h): f0 = log of the
+    mean mu, f1 = log of the dispersion ("size") r = clip(exp(f1), 1e-9, 1e9), so that Var[y | f] = mu + mu^2 / r and f1 -> +inf is
+    Poisson.  Y is one column of non-negative integers (anything else is refused by the library).  There is no parameter of its
+    own: the dispersion is the second latent function.  `predictive` is a closed form; `samples` draws the Gamma-Poisson mixture.
+    The links are fixed (`gp_link` is accepted for the reference's signature and not used)."""
+    name = "NegBinomial"
+    _dims = (1, 2, 1)
+
+    def __init__(self, gp_link=None):
+        pass
+
+
 class Categorical(_Lik):
     name = "Categorical"
 

@@ -4,7 +4,8 @@ task's likelihood; inducing inputs on a grid; lengthscale = c * (inducing spacin
 conditioned at large M.  Used by bench.py, smoke() and the size-property tests."""
 import numpy as np
 
-_DIM_F = dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1)
+_DIM_F = dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1,
+              NegBinomial=2)
 
 
 def _dim_f(name, kw):
@@ -43,6 +44,9 @@ def _sample(rng, name, kw, F):
     if name == "Student":
         nu = kw.get("deg_free", 5.0)
         return F[:, :1] + np.exp(0.5 * F[:, 1:2]) * rng.standard_t(nu, (n, 1))
+    if name == "NegBinomial":                  # Gamma-Poisson mixture: mean exp(f0), size exp(f1)
+        r = np.exp(np.clip(F[:, 1:2], -2, 3))
+        return rng.poisson(np.exp(np.clip(F[:, :1], -5, 3)) * rng.gamma(r) / r).astype(float)
     if name == "Ordinal":                      # labels 1..K drawn from the model; F spread so that every class occurs
         from .engine import ordinal_edges
         edges = ordinal_edges(kw.get("K"), kw.get("bin_edges"))

@@ -45,8 +45,16 @@ enum {
   HMOGP_LIK_BETA = 7,        /* beta.py                                               dim_f = 2   */
   HMOGP_LIK_STUDENT = 8,     /* student.py      param = deg_free nu (finite, > 0)     dim_f = 2   */
   HMOGP_LIK_ORDINAL = 9,     /* ordinal.py      param = id from hmogp_ordinal_table   dim_f = 1   */
-  HMOGP_LIK_DIRICHLET = 10   /* dirichlet.py    param = K (2 .. HMOGP_DIRICHLET_MAXK)  dim_f = K, Y is [N, K] */
+  HMOGP_LIK_DIRICHLET = 10,  /* dirichlet.py    param = K (2 .. HMOGP_DIRICHLET_MAXK)  dim_f = K, Y is [N, K] */
+  HMOGP_LIK_NEGBINOMIAL = 11 /* (not in the reference)  no param (0.0 is passed and ignored)  dim_f = 2 */
 };
+
+/* Negative Binomial: counts with their own dispersion, f0 = log of the mean mu, f1 = log of the size
+ * r = clip(exp(f1), 1e-9, 1e9), Var[y | f] = mu + mu^2 / r (f1 -> +inf is Poisson):
+ *   log p(y | f) = lgamma(y + r) - lgamma(r) - lgamma(y + 1) + y z - (r + y) softplus(z),   z = f0 - log r.
+ * Y is one column of finite, non-negative, integer-valued doubles; anything else is HMOGP_E_INVALID ("NegBinomial" in the message) in
+ * hmogp_set_task_data and in every building block that takes y (hmogp_var_exp[_ex], hmogp_log_predictive).  The family has no
+ * parameter of its own: hmogp_lik_param_count answers 0 and hmogp_var_exp_dparam refuses it.  New enum value only: ABI version 8 stays. */
 
 /* Ordinal (ordered probit): most classes K of one table, and most distinct tables one process can register */
 #define HMOGP_ORDINAL_MAXK 32

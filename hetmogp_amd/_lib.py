@@ -19,8 +19,9 @@ ORDINAL_MAXK = 32
 LIK_DIRICHLET = 10       # compositions on the open simplex (the reference's likelihoods/dirichlet.py stub); lik_param = K, Y is (N, K)
 DIRICHLET_MAXK = 4
 LIK_NEGBINOMIAL = 11     # heteroscedastic Negative Binomial for over-dispersed counts (not in the reference); no lik_param
+LIK_WEIBULL = 12         # Weibull with right-censoring (not in the reference); no lik_param, Y is (N, 2) = (time, event indicator)
 LIK_IDS_BY_NAME = dict(Gaussian=0, Bernoulli=1, HetGaussian=2, Categorical=3, Poisson=4, Exponential=5, Gamma=6, Beta=7,
-                       Student=8, Ordinal=9, Dirichlet=10, NegBinomial=11)
+                       Student=8, Ordinal=9, Dirichlet=10, NegBinomial=11, Weibull=12)
 E_INVALID, E_NO_DEVICE, E_NOT_PD, E_SQI_UNSTABLE, E_STATE, E_COMM = -1, -2, -3, -4, -5, -6
 NTIMINGS = 11
 COMM_ID_BYTES = 128

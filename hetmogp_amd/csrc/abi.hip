@@ -40,7 +40,15 @@ void need_device(int device) {
 // y [N] of a building block -> device.  Ordinal: the labels are checked and replaced by the rows' lower, then upper cut points
 // ([2][N], what launch_var_exp / launch_log_predictive read), so that the device code is the engine's.  Dirichlet: y is [N][K]; it is
 // checked and replaced by log y_k as [K][N], the engine's layout.  Negative Binomial: the counts are checked and uploaded as they are.
+// Weibull: y is [N][2] = (y, delta); it is checked and replaced by (log y, delta) as [2][N], the engine's layout.
 void upload_y(int lik_id, double lik_param, const double* y, long long N, DevBuf& dy) {
+  if (lik_id == HMOGP_LIK_WEIBULL) {
+    std::vector<double> img(2 * (size_t)N);
+    weibull_check_rows(y, N, img.data());
+    dy.ensure(sizeof(double) * 2 * N);
+    HIP_TRY(hipMemcpy(dy.p, img.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
+    return;
+  }
   if (lik_id == HMOGP_LIK_DIRICHLET) {
     const int K = (int)lik_param;
     std::vector<double> ly((size_t)K * N);
@@ -571,7 +579,7 @@ int hmogp_sample(int32_t device, int32_t lik_id, double lik_param, int64_t N, ui
     const int J = lik_dimf(lik_id, lik_param);
     check_lik_param(lik_id, lik_param);
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !F || !Y) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
-    const int Jy = lik_id == HMOGP_LIK_DIRICHLET ? J : 1;   // columns of Y
+    const int Jy = lik_id == HMOGP_LIK_DIRICHLET ? J : 1;   // columns of Y (Weibull: event times only, one column)
     DevBuf dF, dY;
     dF.ensure(sizeof(double) * N * J), dY.ensure(sizeof(double) * N * Jy);
     HIP_TRY(hipMemcpy(dF.p, F, sizeof(double) * N * J, hipMemcpyHostToDevice));

@@ -208,6 +208,10 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
     dirichlet_log_rows(k.dimf, Y, N, cuts.data());
   }
   if (k.lik == HMOGP_LIK_NEGBINOMIAL && N > 0) negbinomial_check_rows(Y, N);   // counts, checked before the task's state changes
+  if (k.lik == HMOGP_LIK_WEIBULL && N > 0) {   // Y is [N, 2] = (y, delta); checked, and (log y, delta) laid out [2][N], before the state changes
+    cuts.resize(2 * (size_t)N);
+    weibull_check_rows(Y, N, cuts.data());
+  }
   k.N = N;
   began = false;
   staged_key.clear();
@@ -226,6 +230,10 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
     k.Ylo.ensure(sizeof(double) * N), k.Yaux.ensure(sizeof(double) * N);
     HIP_TRY(hipMemcpy(k.Ylo.p, cuts.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(k.Yaux.p, cuts.data() + N, sizeof(double) * N, hipMemcpyHostToDevice));
+  }
+  if (k.lik == HMOGP_LIK_WEIBULL) {   // log y depends on the data only, like gammaln(y+1) above
+    k.Ylo.ensure(sizeof(double) * 2 * N);
+    HIP_TRY(hipMemcpy(k.Ylo.p, cuts.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
   }
   if (k.lik == HMOGP_LIK_DIRICHLET) {
     k.Ylo.ensure(sizeof(double) * N * k.dimf);

@@ -105,9 +105,10 @@ struct Task {
   int lik = 0, dimf = 1, d0 = 0;
   double param = 0.0;
   double qparam = 0.0;   // what the quadrature kernels get as lik_param: `param`, but sigma for Ordinal (whose param is a table id)
-  const double* quad_y() const { return (lik == HMOGP_LIK_ORDINAL || lik == HMOGP_LIK_DIRICHLET) ? Ylo.d() : Y.d(); }   // first per-row value of the quadrature
-  long long quad_ldy() const { return lik == HMOGP_LIK_DIRICHLET ? N : 0; }   // row stride of quad_y() where a row has K values (QuadArgs::ldy)
-  int dimy() const { return lik == HMOGP_LIK_DIRICHLET ? dimf : 1; }          // columns of the task's Y
+  // Weibull: Ylo is the [2][N] image (log y, delta) of the task's [N, 2] Y
+  const double* quad_y() const { return (lik == HMOGP_LIK_ORDINAL || lik == HMOGP_LIK_DIRICHLET || lik == HMOGP_LIK_WEIBULL) ? Ylo.d() : Y.d(); }   // first per-row value of the quadrature
+  long long quad_ldy() const { return (lik == HMOGP_LIK_DIRICHLET || lik == HMOGP_LIK_WEIBULL) ? N : 0; }   // row stride of quad_y() where a row has several values (QuadArgs::ldy)
+  int dimy() const { return lik == HMOGP_LIK_DIRICHLET ? dimf : (lik == HMOGP_LIK_WEIBULL ? 2 : 1); }   // columns of the task's Y
   DevBuf offsets;  // device: quad scalar slot -> bundle offset
   int nscal = 0;
   // Ordinal, after hmogp_set_lik_params: the task's PRIVATE table replaces the registry entry `param` names
@@ -141,6 +142,8 @@ void check_lik_param(int lik, double param);  // HMOGP_E_INVALID for a parameter
 // Dirichlet: compositions y [N][K] (every y_k finite and > 0, |sum_k y_k - 1| <= 1e-6, else HMOGP_E_INVALID) -> ly [K][N] = log y_k
 void dirichlet_log_rows(int K, const double* y, long long N, double* ly);
 void negbinomial_check_rows(const double* y, long long N);   // HMOGP_E_INVALID unless every y is a finite, non-negative integer
+// Weibull: rows (y, delta) [N][2] (y finite and > 0, delta exactly 0 or 1, else HMOGP_E_INVALID) -> img [2][N] = log y, delta
+void weibull_check_rows(const double* y, long long N, double* img);
 // Ordinal: labels y [N] (integers in 1..K, else HMOGP_E_INVALID) -> the rows' lower / upper cut points (-inf / +inf at the ends)
 void ordinal_row_cuts(const OrdinalTable& tb, const double* y, long long N, double* lo, double* hi);
 // registers (or finds) a table; returns the value to pass as lik_param

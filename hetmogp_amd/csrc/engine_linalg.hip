@@ -19,7 +19,8 @@ int lik_dimf(int lik, double param) {
     case HMOGP_LIK_GAMMA:
     case HMOGP_LIK_BETA:
     case HMOGP_LIK_STUDENT:
-    case HMOGP_LIK_NEGBINOMIAL: return 2;
+    case HMOGP_LIK_NEGBINOMIAL:
+    case HMOGP_LIK_WEIBULL: return 2;
     case HMOGP_LIK_CATEGORICAL: return (int)param - 1;
     case HMOGP_LIK_DIRICHLET: return (param >= 2.0 && param <= (double)HMOGP_DIRICHLET_MAXK) ? (int)param : -1;
     default: return -1;
@@ -39,6 +40,18 @@ void negbinomial_check_rows(const double* y, long long N) {
   for (long long n = 0; n < N; ++n)
     if (!(std::isfinite(y[n]) && y[n] >= 0.0 && y[n] == std::floor(y[n])))
       throw EngineError{HMOGP_E_INVALID, "NegBinomial: every y must be a finite, non-negative integer"};
+}
+
+// ------------------------------------------------------------------------------------ Weibull rows
+void weibull_check_rows(const double* y, long long N, double* img) {
+  for (long long n = 0; n < N; ++n) {
+    const double t = y[2 * n], d = y[2 * n + 1];
+    if (!(std::isfinite(t) && t > 0.0)) throw EngineError{HMOGP_E_INVALID, "Weibull: every time y must be finite and > 0"};
+    if (!(d == 0.0 || d == 1.0))
+      throw EngineError{HMOGP_E_INVALID, "Weibull: every event indicator must be exactly 1 (observed) or 0 (right-censored)"};
+    img[n] = std::log(t);
+    img[N + n] = d;
+  }
 }
 
 // ------------------------------------------------------------------------------------ Dirichlet rows

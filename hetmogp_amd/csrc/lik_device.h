@@ -2,14 +2,14 @@
 // the mean / variance of q(f), for the eight likelihoods of /root/reference/likelihoods/*.py (SURVEY.md 8a, rows
 // L1-L8), the heteroscedastic Student-t the reference only stubs (student.py; contract: DESIGN 9) and the Ordinal (ordered
 // probit) likelihood it only stubs as well (ordinal.py; contract: DESIGN 9b; no clip), and the Dirichlet likelihood, its third stub
-// (dirichlet.py; contract: DESIGN 9d; K log y_k per row), and the heteroscedastic Negative Binomial, which the reference does not have
-// (contract: DESIGN 9h).  Results reproduce the reference's formulas including its clips and quirks:
+// (dirichlet.py; contract: DESIGN 9d; K log y_k per row), and the heteroscedastic Negative Binomial and the right-censored Weibull, which
+// the reference does not have (contracts: DESIGN 9h, 9i).  Results reproduce the reference's formulas including its clips and quirks:
 //   Q1  Gamma / Beta: Gauss-Hermite weights divided by sqrt(pi) twice (gamma.py:110,139-141; beta.py:113,142-144)
 //   Q2  Categorical: d/dm is the constant onehot(y)[d] - 1 (categorical.py:102-113)
 // At the end of the file: the derivatives with respect to the likelihoods' OWN parameters (Gaussian sigma, Student nu, Ordinal cut
 // points and sigma), appended so that nothing above them changes.
 // Lane mapping: closed forms, 1-D quadratures and Gamma (separable in its two functions) use ONE lane per row;
-// Beta (100 nodes), Student and Negative Binomial (400 nodes), Categorical (10^(K-1) nodes) and Dirichlet (10^K nodes) use ONE WAVE per row,
+// Beta (100 nodes), Student, Negative Binomial and Weibull (400 nodes), Categorical (10^(K-1) nodes) and Dirichlet (10^K nodes) use ONE WAVE per row,
 // nodes strided over the 64 lanes and reduced with wavefront shuffles.
 #pragma once
 #include "common.h"
@@ -228,7 +228,8 @@ __device__ __forceinline__ void lik_ordinal_predictive(const OrdinalTable& tb, d
 // [160,170) normalised GH weights; Beta [0,80) a_i, psi(a_i), zeta(2,a_i), lgamma(a_i) and the same four for b_j;
 // Student [0,60) r_i = y - f0(node i), f1(node j), s_j = exp(-f1(node j)); Dirichlet [0,40) a_k(node i), [40,50) weights,
 // [56,64) m_k, v_k (predictive, T = 20: [0,80) a_k(node i), [80,88) m_k, v_k); Negative Binomial [0,20) min(f0(node i), LIM_VAL), then
-// per node j of f1: [20,40) log r_j, [40,60) r_j, [60,80) G_j - lgamma(y+1), [80,100) r_j D1_j, [100,120) r_j^2 D2_j.
+// per node j of f1: [20,40) log r_j, [40,60) r_j, [60,80) G_j - lgamma(y+1), [80,100) r_j D1_j, [100,120) r_j^2 D2_j;
+// Weibull [0,20) log y - f0(node i), [20,40) k_j, [40,60) log k_j.
 #define HMOGP_ETAB 176
 
 __device__ __forceinline__ double wave_min(double v) {
@@ -555,6 +556,77 @@ __device__ __forceinline__ void lik_negbinomial_wave(double y, double lgy1, cons
   o.gm[1] = wave_sum(g1);
   o.gv[0] = 0.5 * wave_sum(h0);
   o.gv[1] = 0.5 * wave_sum(h1);
+}
+
+// ------------------------------------------------------------------------------------------- Weibull with right-censoring, 20 x 20
+// DESIGN 9i (no counterpart in the reference): a time to an event y > 0 with the indicator delta = 1 (the event was observed at y) or
+// 0 (right-censored: the event is later than y).  f0 = log of the scale lambda, f1 = log of the shape
+// k = clip(safe_exp(f1), 1e-3, 1e3), lk = log k.  With ly = log y (formed once per row on the host), z = min(k (ly - f0), 680),
+// e = exp(z) = (y / lambda)^k (never formed by pow: y^k overflows where the quotient does not):
+//   log p   = delta (lk - ly + z) - e            (delta = 0: the log survival function -e)
+//   d/df0   = k (e - delta)                      d2/df0^2 = -k^2 e
+//   d/df1   = delta (1 + z) - e z                d2/df1^2 = z (delta - e - e z)      (the clips are ignored in the derivatives)
+// The clip of z keeps every addend finite: k^2 e <= 1e301.4, e z^2 <= 1e301.  delta is 0.0 or 1.0 exactly (checked on the host),
+// so the products with it are exact and the row needs no branch.
+#define HMOGP_WEIBULL_ZMAX 680.0
+__device__ __forceinline__ double weibull_shape(double f1) { return clip(safe_exp(f1), 1e-3, 1e3); }
+
+// The full log p at one f (Monte-Carlo log predictive): a censored row scores its survival probability
+__device__ __forceinline__ double lik_weibull_logpdf(double ly, double delta, const double* f) {
+  const double k = weibull_shape(f[1]);
+  const double z = fmin(k * (ly - f[0]), HMOGP_WEIBULL_ZMAX);
+  return delta * (log(k) - ly + z) - exp(z);
+}
+
+// 20 x 20 Gauss-Hermite tensor rule, weights w/sqrt(pi) once per dimension (Student's convention).  Lanes 0-19 write ly - f0(node i) into
+// the wave's LDS slice, lanes 20-39 k_j and lk_j; each of the 400 nodes then costs one exp.
+__device__ __forceinline__ void lik_weibull_wave(double ly, double delta, const double* m, const double* v, int lane, double* tab,
+                                                 LikOut& o) {
+  static_assert(60 <= HMOGP_ETAB, "Weibull table");
+  if (lane < 40) {
+    const int dim = lane / 20, i = lane - 20 * dim;
+    const double f = GH20_X[i] * sqrt(2.0 * v[dim]) + m[dim];
+    if (dim == 0) {
+      tab[i] = ly - f;
+    } else {
+      const double k = weibull_shape(f);
+      tab[20 + i] = k;
+      tab[40 + i] = log(k);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();  // written and read by this wave only (LDS operations of a wave are in order)
+  double ve = 0.0, g0 = 0.0, g1 = 0.0, h0 = 0.0, h1 = 0.0;
+  for (int n = lane; n < 400; n += 64) {
+    const int i = n / 20, j = n - 20 * i;
+    const double w = GH20_WN[i] * GH20_WN[j];
+    const double k = tab[20 + j];
+    const double z = fmin(k * tab[i], HMOGP_WEIBULL_ZMAX), e = exp(z), ez = e * z;
+    ve += w * (delta * (tab[40 + j] - ly + z) - e);
+    g0 += w * (k * (e - delta));
+    h0 -= w * (k * k * e);
+    g1 += w * (delta * (1.0 + z) - ez);
+    h1 += w * (z * (delta - e - ez));
+  }
+  o.ve = wave_sum(ve);
+  o.gm[0] = wave_sum(g0);
+  o.gm[1] = wave_sum(g1);
+  o.gv[0] = 0.5 * wave_sum(h0);
+  o.gv[1] = 0.5 * wave_sum(h1);
+}
+
+// Predictive moments of the event time under independent q(f0), q(f1): E[lambda^p] in closed form, E[Gamma(1 + p / k)] by the
+// 20-node rule over f1 (lgamma, then exp); no clip of the result: overflow is +inf.
+__device__ __forceinline__ void lik_weibull_predictive(const double* m, const double* v, double& mean, double& var) {
+  const double s1 = sqrt(2.0 * v[1]);
+  double g1 = 0.0, g2 = 0.0;
+  for (int j = 0; j < 20; ++j) {
+    const double ik = 1.0 / weibull_shape(GH20_X[j] * s1 + m[1]);
+    g1 += GH20_WN[j] * exp(lgamma(1.0 + ik));
+    g2 += GH20_WN[j] * exp(lgamma(1.0 + 2.0 * ik));
+  }
+  mean = exp(m[0] + 0.5 * v[0]) * g1;
+  const double e2 = exp(2.0 * m[0] + 2.0 * v[0]) * g2;
+  var = e2 < INFINITY ? e2 - mean * mean : INFINITY;
 }
 
 // ------------------------------------------------------------------------------------------- Categorical
@@ -904,6 +976,8 @@ __device__ __forceinline__ void lik_predictive(const double* m, const double* v,
     const double mu = exp(m[0] + 0.5 * v[0]);
     mean[0] = mu;
     var[0] = mu + exp(2.0 * m[0] + 2.0 * v[0] - m[1] + 0.5 * v[1]) + (v[0] > 0.0 ? expm1(v[0]) * exp(2.0 * m[0] + v[0]) : 0.0);
+  } else if (LIK == HMOGP_LIK_WEIBULL) {  // one lane per row, GH20 over f1
+    lik_weibull_predictive(m, v, mean[0], var[0]);
   } else {  // Categorical, categorical.py:84-99,224-269: E[rho_d], rho normalised over the K-1 columns; variance zeros
     const int D = (int)param - 1;
     for (int e = lane; e < D * 10; e += 64) {
@@ -1065,6 +1139,8 @@ __device__ __forceinline__ double lik_logpdf_sample(double y, double yaux, const
     return lp;
   } else if (LIK == HMOGP_LIK_NEGBINOMIAL) {  // yaux = lgamma(y + 1)
     return lik_negbinomial_logpdf(y, yaux, f);
+  } else if (LIK == HMOGP_LIK_WEIBULL) {  // y = log of the time, yaux = delta
+    return lik_weibull_logpdf(y, yaux, f);
   }
   return nan("");
 }
@@ -1170,6 +1246,8 @@ __device__ __forceinline__ double lik_sample(RowRng& g, const double* f, double 
   } else if (LIK == HMOGP_LIK_NEGBINOMIAL) {  // Gamma-Poisson mixture: lambda = mu Gamma(r, 1) / r, y ~ Poisson(lambda)
     const double r = clip(safe_exp(f[1]), 1e-9, 1e9);
     return g.poisson(safe_exp(f[0]) * g.gamma(r) / r);
+  } else if (LIK == HMOGP_LIK_WEIBULL) {  // inversion of the survival function: an event time, never censored
+    return safe_exp(f[0]) * pow(-log(g.uniform()), 1.0 / weibull_shape(f[1]));
   } else {  // Categorical: labels 1..K, probabilities clipped then renormalised (categorical.py:66-71)
     const int K = (int)param, D = K - 1;
     double e[HMOGP_MAXJ], esum = 0.0;
@@ -1244,7 +1322,7 @@ __host__ __device__ constexpr int lik_pred_lanes(int lik) {
 // lanes per row of a likelihood
 __host__ __device__ constexpr int lik_lanes(int lik) {
   return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_STUDENT || lik == HMOGP_LIK_DIRICHLET ||
-          lik == HMOGP_LIK_NEGBINOMIAL)
+          lik == HMOGP_LIK_NEGBINOMIAL || lik == HMOGP_LIK_WEIBULL)
              ? 64
              : 1;
 }
@@ -1272,6 +1350,8 @@ __device__ __forceinline__ void lik_eval(double y, double yaux, const double* m,
     lik_ordinal(y, yaux, m[0], v[0], param, o);   // y / yaux: the row's lower / upper cut point, param: sigma
   else if (LIK == HMOGP_LIK_NEGBINOMIAL)
     lik_negbinomial_wave(y, yaux, m, v, lane, etab, o);   // yaux: lgamma(y + 1)
+  else if (LIK == HMOGP_LIK_WEIBULL)
+    lik_weibull_wave(y, yaux, m, v, lane, etab, o);   // y: log of the time, yaux: delta
   else
     lik_categorical_t<(CATD > 0 ? CATD : 1)>(y, m, v, lane, etab, quirks, o);
   if ((LIK == HMOGP_LIK_GAMMA || LIK == HMOGP_LIK_BETA) && !(quirks & HMOGP_QUIRK_GAMMA_BETA_PI)) {

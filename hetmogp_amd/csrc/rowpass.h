@@ -47,7 +47,8 @@ struct QuadArgs {
   const double* pg = nullptr;          // [Q][ldn] or nullptr (= p)
   const double* cg = nullptr;          // [Q][ldn] or nullptr (= c)
   // Dirichlet: `y` is row 0 of the task's [K][ldy] array of log y_k, offset to the chunk's first row like every per-row
-  // vector; ldy is the task's own row count, whatever slice of it the chunk is.  No other likelihood reads it.
+  // vector; ldy is the task's own row count, whatever slice of it the chunk is.  Weibull: `y` is row 0 of the task's
+  // [2][ldy] image (log y, delta); delta = y[ldy + n] takes the place of yaux.  No other likelihood reads it.
   long long ldy = 0;
 };
 
@@ -107,7 +108,7 @@ struct QuadSeg {
   const double* yaux = nullptr;
   unsigned blk0 = 0;                     // first block of the segment        } filled by launch_quad_multi
   long long part0 = 0;                   // its first word in `partials`      }
-  long long ldy = 0;                     // Dirichlet: row stride of y = log y_k [K][ldy] (QuadArgs::ldy)
+  long long ldy = 0;                     // Dirichlet: row stride of y = log y_k [K][ldy]; Weibull: of (log y, delta) [2][ldy] (QuadArgs::ldy)
 };
 struct QuadMulti {
   int nseg = 0, Q = 1, Df = 0;

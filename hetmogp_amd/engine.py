@@ -14,7 +14,7 @@ from ._lib import lib, check
 LIK_IDS = dict(Gaussian=_lib.LIK_GAUSSIAN, Bernoulli=_lib.LIK_BERNOULLI, HetGaussian=_lib.LIK_HETGAUSSIAN,
                Categorical=_lib.LIK_CATEGORICAL, Poisson=_lib.LIK_POISSON, Exponential=_lib.LIK_EXPONENTIAL,
                Gamma=_lib.LIK_GAMMA, Beta=_lib.LIK_BETA, Student=_lib.LIK_STUDENT, Ordinal=_lib.LIK_ORDINAL,
-               Dirichlet=_lib.LIK_DIRICHLET, NegBinomial=_lib.LIK_NEGBINOMIAL)
+               Dirichlet=_lib.LIK_DIRICHLET, NegBinomial=_lib.LIK_NEGBINOMIAL, Weibull=_lib.LIK_WEIBULL)
 
 
 def _f64(a):
@@ -32,17 +32,21 @@ def lik_dim_f(name, **kw):
     if name == "Dirichlet":
         return int(kw["K"])
     return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1,
-                NegBinomial=2)[name]
+                NegBinomial=2, Weibull=2)[name]
 
 
 def lik_dim_y(name, **kw):
-    """Columns of a task's Y (the reference's ``get_metadata()[0]``): 1, but K for a Dirichlet task."""
-    return int(kw["K"]) if name == "Dirichlet" else 1
+    """Columns of a task's Y (the reference's ``get_metadata()[0]``): 1, but K for a Dirichlet task and 2 (time, event
+    indicator) for a Weibull task."""
+    return int(kw["K"]) if name == "Dirichlet" else (2 if name == "Weibull" else 1)
 
 
 def _y_rows(name, y, **kw):
-    """y of one task as the library reads it: (N,), or (N, K) row-major for a Dirichlet task."""
+    """y of one task as the library reads it: (N,), or (N, K) row-major for a Dirichlet task, (N, 2) for a Weibull task (whose second
+    column is a flag, not an observation: an array of any other shape is refused instead of being reshaped into pairs)."""
     dy = lik_dim_y(name, **kw)
+    if name == "Weibull" and (np.ndim(y) != 2 or np.shape(y)[1] != 2):
+        raise _lib.InvalidArgument("Weibull: Y must be (N, 2) = (time, event indicator), got shape %r" % (np.shape(y),))
     return _f64(y).reshape(-1) if dy == 1 else _f64(y).reshape(-1, dy)
 
 
@@ -598,10 +602,10 @@ def log_predictive_rows(name, y, m, v, num_samples=1000, seed=0, device=None, **
 
 def sample(name, F, seed=0, device=None, **kw):
     """One draw y ~ p(y | F[n]) per row on the device (the reference's `<likelihood>.samples`): returns (N, 1); (N, K) for
-    Dirichlet."""
+    Dirichlet.  Weibull: event times (N, 1), never censored."""
     device = _resolve_device(device)
     J = lik_dim_f(name, **kw)
     F = _f64(F).reshape(-1, J)
-    Y = np.zeros((F.shape[0], lik_dim_y(name, **kw)))
+    Y = np.zeros((F.shape[0], 1 if name == "Weibull" else lik_dim_y(name, **kw)))
     check(lib.hmogp_sample(device, LIK_IDS[name], lik_param(name, **kw), F.shape[0], int(seed) & (2 ** 64 - 1), _p(F), _p(Y)))
     return Y

@@ -5,7 +5,7 @@ conditioned at large M.  Used by bench.py, smoke() and the size-p
 import numpy as np
 
 _DIM_F = dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1,
-              NegBinomial=2)
+              NegBinomial=2, Weibull=2)
 
 
 def _dim_f(name, kw):
@@ -47,6 +47,8 @@ def _sample(rng, name, kw, F):
     if name == "NegBinomial":                  # Gamma-Poisson mixture: mean exp(f0), size exp(f1)
         r = np.exp(np.clip(F[:, 1:2], -2, 3))
         return rng.poisson(np.exp(np.clip(F[:, :1], -5, 3)) * rng.gamma(r) / r).astype(float)
+    if name == "Weibull":                      # (time, event indicator): censored at an independent Weibull censoring time
+        return weibull_censored(rng, np.clip(F[:, :1], -3, 3), np.clip(F[:, 1:2], -1, 1.5), kw.get("censored", 0.3))
     if name == "Ordinal":                      # labels 1..K drawn from the model; F spread so that every class occurs
         from .engine import ordinal_edges
         edges = ordinal_edges(kw.get("K"), kw.get("bin_edges"))
@@ -63,6 +65,23 @@ def _sample(rng, name, kw, F):
         p = np.hstack([e, np.ones((n, 1))]) / (1.0 + e.sum(1, keepdims=True))
         return (1 + (rng.rand(n, 1) > np.cumsum(p, 1)).sum(1, keepdims=True)).astype(float).clip(1, K)
     raise ValueError(name)
+
+
+def weibull_censored(rng, f0, f1, censored=0.3):
+    """(N, 2) rows (y, delta) of a Weibull task: event times t = exp(f0) (-log U)^(1 / k), k = exp(f1), censored at an independent
+    censoring time c = s exp(f0) (-log U')^(1 / k): y = min(t, c), delta = 1 where t <= c.  With the same scale function and shape,
+    (t / c)^k is a ratio of two unit exponentials times s^-k, so P(censored) = 1 / (1 + s^k) for every row; s is chosen per row to
+    make that the stated share `censored` (0 <= censored < 1; 0: no row is censored)."""
+    f0, f1 = np.asarray(f0, float).reshape(-1, 1), np.asarray(f1, float).reshape(-1, 1)
+    if not 0.0 <= censored < 1.0:
+        raise ValueError("censored must lie in [0, 1), got %r" % (censored,))
+    ik = 1.0 / np.exp(f1)
+    t = np.exp(f0) * (-np.log(1.0 - rng.rand(*f0.shape))) ** ik
+    u = -np.log(1.0 - rng.rand(*f0.shape))
+    if censored == 0.0:
+        return np.hstack([t, np.ones_like(t)])
+    c = np.exp(f0) * ((1.0 - censored) / censored * u) ** ik          # s^k = (1 - censored) / censored
+    return np.hstack([np.minimum(t, c), (t <= c).astype(float)])
 
 
 def make_case(specs, Ns, M, Q, P=1, seed=0, c=(0.8, 1.0, 1.3, 1.1, 0.9, 1.2, 1.0, 0.85)):

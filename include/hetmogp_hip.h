@@ -46,8 +46,18 @@ enum {
   HMOGP_LIK_STUDENT = 8,     /* student.py      param = deg_free nu (finite, > 0)     dim_f = 2   */
   HMOGP_LIK_ORDINAL = 9,     /* ordinal.py      param = id from hmogp_ordinal_table   dim_f = 1   */
   HMOGP_LIK_DIRICHLET = 10,  /* dirichlet.py    param = K (2 .. HMOGP_DIRICHLET_MAXK)  dim_f = K, Y is [N, K] */
-  HMOGP_LIK_NEGBINOMIAL = 11 /* (not in the reference)  no param (0.0 is passed and ignored)  dim_f = 2 */
+  HMOGP_LIK_NEGBINOMIAL = 11, /* (not in the reference)  no param (0.0 is passed and ignored)  dim_f = 2 */
+  HMOGP_LIK_WEIBULL = 12      /* (not in the reference)  no param (0.0 is passed and ignored)  dim_f = 2, Y is [N, 2] */
 };
+
+/* Weibull with right-censoring: times to an event that may be only partly observed.  f0 = log of the scale lambda,
+ * f1 = log of the shape k = clip(exp(f1), 1e-3, 1e3).  Y is [N, 2] row-major: (y, delta), y finite and > 0, delta exactly 1.0 (the
+ * event was observed at y) or 0.0 (right-censored: the event is later than y).  With z = min(k (log y - f0), 680), e = exp(z):
+ *   log p(y, delta | f) = delta (log k - log y + z) - e       (delta = 0: the log survival function -e).
+ * Anything else in Y is HMOGP_E_INVALID ("Weibull" in the message) in hmogp_set_task_data (the task keeps its previous data) and in
+ * every building block that takes y (hmogp_var_exp[_ex], hmogp_log_predictive, whose y is [N, 2] as well).  hmogp_sample writes
+ * event times [N, 1] (never censored); hmogp_predictive the mean and variance of the event time.  The family has no parameter of its
+ * own: hmogp_lik_param_count answers 0 and hmogp_var_exp_dparam refuses it.  New enum value only: ABI version 8 stays. */
 
 /* Negative Binomial: counts with their own dispersion, f0 = log of the mean mu, f1 = log of the size
  * r = clip(exp(f1), 1e-9, 1e9), Var[y | f] = mu + mu^2 / r (f1 -> +inf is Poisson):

@@ -16,7 +16,9 @@ kinds ve, sgv, H, r, dZ, sa, sl, swk, dKmn, dKdiag, m, v.  `check` prints the wo
 Constants.  C_ORACLE[kind] = the largest |oracle - R| / (2^-52 S) of the float64 NumPy oracle (`so.u_algebra` + `so.local_stats`, BLAS /
 LAPACK) over cases A-E with case D's batch-scale, row-shard and strict variants, rounded up to the next power of two: what plain float64 achieves on these
 formulas (tests/test_rowpass_ref_cpu.py measures it and asserts it).  The kernels get C_KERNEL = max(16, 4 * C_ORACLE): another
-summation order, MFMA accumulation, special functions with 1-2 ulp.  Against the float64 oracle instead of R the two constants add."""
+summation order, MFMA accumulation, special functions with 1-2 ulp.  Against the float64 oracle instead of R the two constants add.
+Cases G, H, I (3-D / 4-D inputs, eight latents) have C_ORACLE_WIDE / C_KERNEL_WIDE: the same rule over their own oracle measurement,
+never below C_ORACLE; cases A-F stay on C_ORACLE / C_KERNEL."""
 import numpy as np
 
 import lik_ref_mp as lr
@@ -36,10 +38,18 @@ C_ORACLE = dict(ve=16.0, sgv=8.0, H=256.0, r=64.0, dZ=4.0, sa=1.0, sl=1.0, swk=1
 # Elements beyond C_KERNEL that are inherent to the formulation: {(case tag, kind): [index tuples]} -- at most 1 % of an array, none in
 # a tile of the 100 h latent, each justified in DESIGN 9c.  None is needed.
 KERNEL_EXCEPTIONS = {}
+# Cases G, H, I (3-D / 4-D inputs, eight latents) and their variants: per kind max(C_ORACLE, the float64 oracle's largest ratio over
+# them rounded up to a power of two), by the same rule and against R (measured 2026-10-19 on the CPU).  Two kinds move, both
+# sums of quadrature rows in NumPy's pairwise order: ve (24.7 on G) and sgv (24.2 on I).  Cases A-F stay on C_ORACLE.
+C_ORACLE_WIDE = dict(C_ORACLE, ve=32.0, sgv=32.0)
 
 
 def c_kernel():
     return {k: max(16.0, 4.0 * c) for k, c in C_ORACLE.items()}
+
+
+def c_kernel_wide():
+    return {k: max(16.0, 4.0 * c) for k, c in C_ORACLE_WIDE.items()}
 
 
 def c_kernel_vs_float64():

@@ -137,7 +137,7 @@ def references():
     with multiprocessing.get_context("spawn").Pool(n) as pool:
         own = [pool.apply_async(_own_case, (tag,)) for tag in sorted(size, key=lambda t: -size[t])]
         todo = {}          # tag -> dict(case, side, variants {name: (bundle, strict)})
-        for tag in sorted(rc.CASES):
+        for tag in rc.BASE_TAGS:
             v = {"default": (dense_bundle(refs, tag), False)}
             if tag == "D":
                 v["bs"] = (dense_bundle(refs, tag, "bs"), False)

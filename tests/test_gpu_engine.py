@@ -235,11 +235,12 @@ def test_q_u_only_evaluation_uses_triangular_fold_and_matches_full():
 ], ids=["M1", "N1", "Q8", "P3", "P4_empty", "T6_2d"])
 def test_odd_shapes_vs_oracle(case):
     """Corner shapes against the NumPy oracle: M = 1, N = 1, Q = 8 latents, 3-D / 4-D inputs, an empty task, six tasks;
-    every one also through row pools smaller than a task (chunk_rows = 48), which must not change anything."""
+    every one also through row pools smaller than a task (chunk_rows = 48), which must not change anything, and a third time with
+    small_path=False: at M <= 64 the first two legs take the fused small-model kernels, the third the regular row-pass kernels."""
     from oracle import svmogp_oracle as so
     prm, prob, X, Y = synth(41, case["specs"], case["Ns"], case["M"], case["Q"], case["P"], case["cs"])
     want = so.elbo_grad_fused(prm, prob, X, Y)
-    for kw in ({}, {"chunk_rows": 48}):
+    for kw in ({}, {"chunk_rows": 48}, {"small_path": False}):
         out = run(make_engine(prob, X, Y, **kw), prm)
         for k in KEYS:
             assert rel(out[k], want[k]) < TOL, (k, kw)

@@ -1,7 +1,8 @@
 """GPU: seeded random configurations against the oracle.  The shapes are drawn so that every dispatch branch of the
 contraction kernels is hit: inducing counts that are / are not multiples of 16, 64 and 128 (specialised 8-wave row-pass
 kernels, general kernel, 64 x 64-tile M x M products), odd and even tile counts (two-phase Gram tile order), one to
-three latents, 1-D and 2-D inputs, ragged / tiny / empty tasks, minibatch ranges, several row pools, both quirk modes."""
+three latents, 1-D and 2-D inputs, ragged / tiny / empty tasks, minibatch ranges, several row pools, both quirk modes; six further
+seeds draw 3-D / 4-D inputs and four to eight latents, two of the three inducing counts beyond the fused small-model kernels."""
 import numpy as np
 import pytest
 
@@ -30,12 +31,25 @@ def test_random_configuration_large_M_vs_oracle(seed):
     _case(seed, MS_LARGE, True)
 
 
-def _case(seed, ms, one_d):
+MS_WIDE = [96, 200, 256]      # fused small-model kernels (M <= 128), general and specialised regular row-pass kernels
+
+
+@pytest.mark.parametrize("seed", range(218, 224))
+def test_random_configuration_3d_4d_inputs_many_latents_vs_oracle(seed):
+    """P in {3, 4} and Q in {4 ... 8}: `rbf_kernel<3|4>`, `colstats_kernel<3|4>`, the row pass batched over more than three latents.
+    (Seeds 218 ... 223 draw (M, P, Q) = (256, 4, 7), (96, 3, 6), (200, 4, 7), (256, 4, 7), (96, 4, 4), (200, 3, 8).)"""
+    _case(seed, MS_WIDE, False, wide=True)
+
+
+def _case(seed, ms, one_d, wide=False):
     from oracle import svmogp_oracle as so
     rng = np.random.RandomState(1000 + seed)
     M = ms[seed % len(ms)]
-    P = 1 if (rng.rand() < 0.7 or one_d) else 2
-    Q = int(rng.randint(1, 4))
+    if wide:
+        P, Q = int(rng.randint(3, 5)), int(rng.randint(4, 9))
+    else:
+        P = 1 if (rng.rand() < 0.7 or one_d) else 2
+        Q = int(rng.randint(1, 4))
     T = int(rng.randint(1, 4))
     specs = [LIKS[i] for i in rng.choice(len(LIKS), T, replace=False)]
     Ns = [int(rng.choice([0, 1, 17, 130, 257, 700, 1500], p=[0.05, 0.05, 0.1, 0.2, 0.2, 0.2, 0.2])) for _ in range(T)]

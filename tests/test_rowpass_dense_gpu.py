@@ -7,7 +7,10 @@ move far beyond the bound
 
 What is read: the statistic bundle between hmogp_step_begin and hmogp_step_finish (lower triangle of H), dL_dKmn / dL_dKdiag of the
 inner-protocol export, and q(f) through hmogp_predict_f (the triangular fold; it uses the factorisation of the evaluation it follows,
-forced rung included).  Every test prints its worst ratios as `[rowpass] <case> <kind> ...`."""
+forced rung included).  Every test prints its worst ratios as `[rowpass] <case> <kind> ...`.
+
+Cases G, H, I take the regular kernels to 3-D and 4-D inputs and to HMOGP_MAXQ latents (`rbf_kernel<3|4>`, `colstats_kernel<3|4, ...>`,
+`window_kernel<3>`, `strict_rowstats_kernel<3|4>`, the row pass batched over eight latents); they are held to C_KERNEL_WIDE."""
 import numpy as np
 import pytest
 
@@ -71,6 +74,11 @@ def evaluate(e, tag, fused=False, raw=True, predict=True, **kw):
     return got
 
 
+def ck(tag):
+    """Cases A-F: C_KERNEL; cases G, H, I: C_KERNEL_WIDE (the same rule over their own oracle measurement)."""
+    return rr.c_kernel_wide() if tag in rc.WIDE_TAGS else rr.c_kernel()
+
+
 def same_bits(a, b, kinds):
     for k in kinds:
         for (label, x, _, _), (_, y, _, _) in zip(rr.pairs(k, a[k], a[k], a[k]), rr.pairs(k, b[k], b[k], b[k])):
@@ -79,12 +87,12 @@ def same_bits(a, b, kinds):
 
 @pytest.mark.parametrize("tag", sorted(rc.CASES))
 def test_dense_case_vs_extended_precision(refs, tag):
-    """Cases A-F on the default engine through the split step: the bundle, the inner-protocol gradients and q(f), every element; a second
+    """Cases A-I on the default engine through the split step: the bundle, the inner-protocol gradients and q(f), every element; a second
     identical evaluation gives the same bits."""
     R, S = refs[tag]["default"]
     e = engine(tag)
     got = evaluate(e, tag)
-    rr.check(tag, got, R, S, rr.c_kernel(), rr.KINDS)
+    rr.check(tag, got, R, S, ck(tag), rr.KINDS)
     same_bits(got, evaluate(e, tag), rr.KINDS)
     e.close()
 
@@ -153,4 +161,55 @@ def test_case_D_strict_one_solve_form(refs):
     e = engine("D", strict_qf=True)
     got = evaluate(e, "D", raw=False, predict=False)
     rr.check("D strict_qf", got, R, S, rr.c_kernel(), rr.BUNDLE_KINDS)
+    e.close()
+
+
+# ------------------------------------------------------------------------------------------------ 3-D / 4-D inputs, eight latents
+def test_case_I_row_pools_of_100(refs):
+    """Eight latents with chunk_rows = 100: several pools, tasks cut into segments, the batched row pass once per pool."""
+    R, S = refs["I"]["default"]
+    e = engine("I", chunk_rows=100)
+    kinds = rr.BUNDLE_KINDS + ("m", "v")
+    got = evaluate(e, "I", raw=False)
+    rr.check("I chunk_rows=100", got, R, S, ck("I"), kinds)
+    same_bits(got, evaluate(e, "I", raw=False), kinds)
+    e.close()
+
+
+@pytest.mark.parametrize("tag", ["G", "H"])
+def test_cases_G_H_strict_one_solve_form(refs, tag):
+    """strict_qf=True at P = 3 and P = 4: `strict_rowstats_kernel<P>` and `colstats_kernel<P, true, ...>`."""
+    R, S = refs[tag]["strict"]
+    e = engine(tag, strict_qf=True)
+    rr.check(tag + " strict_qf", evaluate(e, tag, raw=False, predict=False), R, S, ck(tag), rr.BUNDLE_KINDS)
+    e.close()
+
+
+def test_case_H_row_shard_off_the_16_row_grid(refs):
+    """P = 4 and a row shard whose first rows are no multiples of 16: the X offset of a task is row_begin * 4 doubles."""
+    R, S = refs["H"]["shard"]
+    e = engine("H")
+    got = evaluate(e, "H", row_begin=list(rc.H_SHARD[0]), row_end=list(rc.H_SHARD[1]))
+    rr.check("H row shard", got, R, S, ck("H"), rr.KINDS)
+    e.close()
+
+
+def test_case_G_exact_zero_windows_cover_everything(refs):
+    """Exact-zero windows asked for explicitly at P = 3 (`window_kernel<3>`, `colstats_kernel<3, ., ., true>`): nothing is exactly
+    zero, the windows must cover every tile (their row ranges refuse the inner-protocol export, which is left out)."""
+    R, S = refs["G"]["default"]
+    e = engine("G", exact_zero_windows=True)
+    rr.check("G exact_zero_windows", evaluate(e, "G", raw=False), R, S, ck("G"), rr.BUNDLE_KINDS + ("m", "v"))
+    e.close()
+
+
+def test_case_G_row_weights_follow_the_evaluation(refs):
+    """Three evaluations on one engine: default, batch_scale = [1, 3.5, 0.25], default again.  The row-weight buffers keep their
+    addresses from one evaluation to the next: `colstats_kernel<3, ., ., false>` reads alpha, alpha0, beta0 through the constant address
+    space and must see the values of the CURRENT evaluation."""
+    e = engine("G")
+    first = evaluate(e, "G")
+    rr.check("G first", first, *refs["G"]["default"], ck("G"), rr.KINDS)
+    rr.check("G then batch_scale", evaluate(e, "G", batch_scale=rc.D_BATCH_SCALE), *refs["G"]["bs"], ck("G"), rr.KINDS)
+    same_bits(first, evaluate(e, "G"), rr.KINDS)
     e.close()

@@ -4,7 +4,9 @@
   (b) the element-wise criterion rejects seeded indexing corruptions of the oracle's own output of case D (arithmetic on arrays:
       nothing is run wrongly), while the array-maximum yardstick of the existing tests accepts a far Gram tile that is transposed or
       never written on the banded case of the same shape;
-  (c) the references of all cases are built once, in a pool of at most 16 processes (printed: about 50 s on 8 CPUs, 25 s on 16)."""
+  (c) the references of all cases are built once, in a pool of at most 16 processes (printed: about 50 s on 8 CPUs, 25 s on 16);
+  (d) cases G, H, I (3-D / 4-D inputs, eight latents) are held to C_ORACLE_WIDE, and the criterion rejects what a wrong X stride, a dZ
+      component at the wrong p, a latent's bundle block at the wrong q or a quadrature that mixes three latents only would leave."""
 import numpy as np
 import pytest
 
@@ -46,6 +48,18 @@ def oracle_outputs(prm, prob, X, Y, rungs, bs=None, row_begin=None, row_end=None
     return got
 
 
+def c_oracle(tag):
+    return rr.C_ORACLE_WIDE if tag in rc.WIDE_TAGS else rr.C_ORACLE
+
+
+def variant_outputs(tag, name, **kw):
+    """The float64 oracle's outputs of one variant of rc.VARIANTS[tag]."""
+    v = dict(rc.VARIANTS[tag][name])
+    if "batch_scale" in v:
+        v["bs"] = v.pop("batch_scale")
+    return oracle_outputs(*rc.dense_case(tag), **v, **kw)
+
+
 def lower_tiles(M):
     return [(i, j) for i in range(0, M, TILE) for j in range(0, i + 1, TILE)]
 
@@ -78,25 +92,28 @@ def test_cases_are_dense_and_well_conditioned(refs, tag):
 @pytest.mark.parametrize("tag", sorted(rc.CASES))
 def test_oracle_within_c_oracle(refs, tag):
     """The float64 oracle against R, every kind, every element: the measurement behind rowpass_ref.C_ORACLE (cases A-E with the batch-scale
-    and shard variants and the strict form of D define it; F is held to the same constants)."""
+    and shard variants and the strict form of D define it; F is held to the same constants) and behind C_ORACLE_WIDE (G, H, I with the
+    batch-scale and strict variants of G and the shard and strict variants of H)."""
     prm, prob, X, Y, rungs = rc.dense_case(tag)
     R, S = refs[tag]["default"]
-    rr.check("oracle " + tag, oracle_outputs(prm, prob, X, Y, rungs), R, S, rr.C_ORACLE, rr.KINDS)
-    if tag == "D":
-        got = oracle_outputs(prm, prob, X, Y, rungs, bs=rc.D_BATCH_SCALE)
-        rr.check("oracle D batch_scale", got, *refs[tag]["bs"], rr.C_ORACLE, rr.KINDS)
-        got = oracle_outputs(prm, prob, X, Y, rungs, row_begin=rc.D_SHARD[0], row_end=rc.D_SHARD[1])
-        rr.check("oracle D row shard", got, *refs[tag]["shard"], rr.C_ORACLE, rr.KINDS)
-        got = oracle_outputs(prm, prob, X, Y, rungs, strict=True)
-        rr.check("oracle D strict", got, *refs[tag]["strict"], rr.C_ORACLE, rr.BUNDLE_KINDS)
+    C = c_oracle(tag)
+    rr.check("oracle " + tag, oracle_outputs(prm, prob, X, Y, rungs), R, S, C, rr.KINDS)
+    names = {"bs": "batch_scale", "shard": "row shard", "strict": "strict"}
+    for name in ("bs", "shard", "strict"):
+        if name in rc.VARIANTS.get(tag, {}):
+            kinds = rr.BUNDLE_KINDS if name == "strict" else rr.KINDS
+            rr.check("oracle %s %s" % (tag, names[name]), variant_outputs(tag, name), *refs[tag][name], C, kinds)
 
 
 def test_constants_follow_the_rule():
-    ck = rr.c_kernel()
-    for k in rr.KINDS:
-        c = rr.C_ORACLE[k]
-        assert c >= 1 and np.log2(c) == int(np.log2(c))          # a power of two
-        assert ck[k] == max(16.0, 4.0 * c)
+    for CO, ck in ((rr.C_ORACLE, rr.c_kernel()), (rr.C_ORACLE_WIDE, rr.c_kernel_wide())):
+        for k in rr.KINDS:
+            c = CO[k]
+            assert c >= 1 and np.log2(c) == int(np.log2(c))          # a power of two
+            assert ck[k] == max(16.0, 4.0 * c)
+    # the wide set only ever adds to the first: max(C_ORACLE, what G, H, I need); ve and sgv are the two kinds that moved
+    assert all(rr.C_ORACLE_WIDE[k] >= rr.C_ORACLE[k] for k in rr.KINDS)
+    assert {k for k in rr.KINDS if rr.C_ORACLE_WIDE[k] != rr.C_ORACLE[k]} == {"ve", "sgv"}
     assert not rr.KERNEL_EXCEPTIONS
 
 
@@ -188,6 +205,57 @@ def test_criterion_rejects_indexing_corruptions(refs):
         with pytest.raises(AssertionError):
             rr.check("corrupted: " + what, got, R, S, CK, (kind,))
     rr.check("uncorrupted D", clean, R, S, CK, rr.KINDS)
+
+
+def test_criterion_rejects_stride_corruptions_at_3d_4d_inputs_and_eight_latents(refs):
+    """Seeded corruptions of the ORACLE's output of cases G, H (row shard) and I, each what a wrong stride in P or Q would leave behind
+    (arithmetic on arrays: nothing is run wrongly).  Each must land beyond C_KERNEL_WIDE; the ratios reached are recorded in DESIGN 9c."""
+    CK = rr.c_kernel_wide()
+    reached = []
+
+    # 1. case H, row shard: task 0's rows read at row_begin * 1 doubles where row_begin * 4 is meant -- its K^-dependent outputs formed
+    #    again from the 264 x 4 doubles that start 37 doubles into X_0
+    prm, prob, X, Y, rungs = rc.dense_case("H")
+    b, e = rc.H_SHARD
+    Xbad = [x.copy() for x in X]
+    Xbad[0][b[0]:e[0]] = X[0].reshape(-1)[b[0]:b[0] + 4 * (e[0] - b[0])].reshape(e[0] - b[0], 4)
+    bad = oracle_outputs(prm, prob, Xbad, Y, rungs, row_begin=b, row_end=e)
+    for kind in ("r", "dZ", "m"):
+        reached.append(("H shard: X_0 offset row_begin * 1", "H", "shard", kind, bad))
+    # 2. case G: the p = 1 and p = 2 components of dZ exchanged for one inducing point
+    clean = oracle_outputs(*rc.dense_case("G"))
+    bad = dict(clean, dZ=clean["dZ"].copy())
+    bad["dZ"][1, 100, [1, 2]] = clean["dZ"][1, 100, [2, 1]]
+    reached.append(("G: dZ components p = 1, 2 exchanged", "G", "default", "dZ", bad))
+    # 3. case I: the bundle blocks of latents 6 and 7 exchanged
+    prm, prob, X, Y, rungs = rc.dense_case("I")
+    keep = {}
+    clean = oracle_outputs(prm, prob, X, Y, rungs, keep=keep)
+    bad = dict(clean)
+    for k in ("H", "r", "dZ", "sa", "sl", "swk"):
+        bad[k] = clean[k].copy()
+        bad[k][[6, 7]] = clean[k][[7, 6]]
+    for kind in ("H", "r"):
+        reached.append(("I: bundle blocks q = 6, 7 exchanged", "I", "default", kind, bad))
+    # 4. case I: the quadrature mixes p_q, c_q of the first three latents only
+    u, W, kap = keep["u"], prm["W"], prm["kappa"]
+    bad = dict(clean, m=[a.copy() for a in clean["m"]], v=[a.copy() for a in clean["v"]])
+    for o in keep["rows"]:
+        t = o["t"]
+        for d in (d for d in range(prob["Df"]) if prob["f_index"][d] == t):
+            for q in range(3, prob["Q"]):
+                p_q, c_q = o["K"][q] @ u["a"][q], np.sum(o["Pt"][q] * o["K"][q], 1)
+                bad["m"][d] -= W[q, d] * p_q
+                bad["v"][d] -= (W[q, d] ** 2 + kap[q, d]) * prm["variance"][q] + W[q, d] ** 2 * c_q
+    for kind in ("m", "v"):
+        reached.append(("I: quadrature over q < 3 only", "I", "default", kind, bad))
+    for what, tag, variant, kind, got in reached:
+        R, S = refs[tag][variant]
+        ratio = rr.worst_ratios(got, R, S, (kind,))[kind][0]
+        print("[rowpass] corruption %-36s %-5s ratio %.3g (C_KERNEL_WIDE = %g)" % (what, kind, ratio, CK[kind]))
+        assert ratio > CK[kind], (what, ratio)
+        with pytest.raises(AssertionError):
+            rr.check("corrupted: " + what, got, R, S, CK, (kind,))
 
 
 def test_array_maximum_yardstick_accepts_far_tile_corruptions_on_the_banded_case():

@@ -133,6 +133,10 @@ EXPORTS = {
                                    c_double_p]),
     "hmogp_log_predictive": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_uint64, c_double_p,
                                        c_double_p, c_double_p, c_double_p]),
+    "hmogp_log_predictive_gh": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, c_double_p, c_double_p,
+                                          c_double_p, c_double_p, c_double_p]),
+    "hmogp_predict_log_density": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_int64, C.c_int32, c_double_p,
+                                            c_double_p]),
     "hmogp_sample": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint64, c_double_p, c_double_p]),
     "hmogp_bench_contraction": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, c_double_p]),
     "hmogp_host_alloc": (C.c_void_p, [C.c_uint64]),

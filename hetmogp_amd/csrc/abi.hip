@@ -37,11 +37,19 @@ void need_device(int device) {
   HIP_TRY(hipSetDevice(device));
 }
 
+void upload_y(int lik_id, double lik_param, const double* y, long long N, DevBuf& dy) {
+  upload_y_image(lik_id, lik_param, nullptr, y, N, dy);
+}
+
+}  // namespace
+
+namespace hmogp_detail {
 // y [N] of a building block -> device.  Ordinal: the labels are checked and replaced by the rows' lower, then upper cut points
 // ([2][N], what launch_var_exp / launch_log_predictive read), so that the device code is the engine's.  Dirichlet: y is [N][K]; it is
 // checked and replaced by log y_k as [K][N], the engine's layout.  Negative Binomial: the counts are checked and uploaded as they are.
 // Weibull: y is [N][2] = (y, delta); it is checked and replaced by (log y, delta) as [2][N], the engine's layout.
-void upload_y(int lik_id, double lik_param, const double* y, long long N, DevBuf& dy) {
+// `tb`: the Ordinal table to cut by instead of the registry entry `lik_param` names (a task's private table).
+void upload_y_image(int lik_id, double lik_param, const OrdinalTable* tb, const double* y, long long N, DevBuf& dy) {
   if (lik_id == HMOGP_LIK_WEIBULL) {
     std::vector<double> img(2 * (size_t)N);
     weibull_check_rows(y, N, img.data());
@@ -64,12 +72,11 @@ void upload_y(int lik_id, double lik_param, const double* y, long long N, DevBuf
     return;
   }
   std::vector<double> cuts(2 * (size_t)N);
-  ordinal_row_cuts(ordinal_table(lik_param), y, N, cuts.data(), cuts.data() + N);
+  ordinal_row_cuts(tb ? *tb : ordinal_table(lik_param), y, N, cuts.data(), cuts.data() + N);
   dy.ensure(sizeof(double) * 2 * N);
   HIP_TRY(hipMemcpy(dy.p, cuts.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
 }
-
-}  // namespace
+}  // namespace hmogp_detail
 
 extern "C" {
 
@@ -569,6 +576,53 @@ int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64
     launch_log_predictive(lik_id, J, lik_param, N, num_samples, seed, dy.d(), dm.d(), dv.d(), dout.d(), nullptr);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(log_pred, dout.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+  });
+}
+
+// nodes per dimension of the deterministic rule: 0 = the default, 20, but 10 for Categorical and Dirichlet, which take no other
+static int lpd_nodes(int lik_id, int gh_T) {
+  const bool tensor10 = lik_id == HMOGP_LIK_CATEGORICAL || lik_id == HMOGP_LIK_DIRICHLET;
+  if (gh_T == 0) return tensor10 ? 10 : 20;
+  if (tensor10 ? gh_T != 10 : (gh_T != 10 && gh_T != 20))
+    throw EngineError{HMOGP_E_INVALID, tensor10 ? "gh_T must be 0 or 10 for Categorical / Dirichlet" : "gh_T must be 0, 10 or 20"};
+  return gh_T;
+}
+
+int hmogp_log_predictive_gh(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, const double* y,
+                            const double* m, const double* v, double* lpd, double* ess) {
+  return guarded(nullptr, [&] {
+    need_device(device);
+    if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
+    const int J = lik_dimf(lik_id, lik_param);
+    check_lik_param(lik_id, lik_param);
+    if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !y || !m || !v || !lpd) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
+    LpdArgs a;
+    a.T = lpd_nodes(lik_id, gh_T);
+    DevBuf dy, dm, dv, dl, de;
+    upload_y(lik_id, lik_param, y, N, dy);
+    dm.ensure(sizeof(double) * N * J), dv.ensure(sizeof(double) * N * J), dl.ensure(sizeof(double) * N);
+    if (ess) de.ensure(sizeof(double) * N);
+    HIP_TRY(hipMemcpy(dm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
+    a.lik = lik_id, a.J = J, a.N = N;
+    a.param = lik_id == HMOGP_LIK_ORDINAL ? ordinal_table(lik_param).sigma : lik_param;
+    a.y = dy.d(), a.ldy = N, a.m = dm.d(), a.v = dv.d(), a.ldf = J;
+    a.lpd = dl.d(), a.ess = ess ? de.d() : nullptr;
+    launch_log_predictive_gh(a, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(lpd, dl.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+    if (ess) HIP_TRY(hipMemcpy(ess, de.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+  });
+}
+
+int hmogp_predict_log_density(hmogp_handle h, int32_t t, const double* Xnew, const double* Ynew, int64_t Nnew, int32_t gh_T,
+                              double* lpd, double* ess) {
+  if (!h) return HMOGP_E_INVALID;
+  return guarded(h, [&] {
+    if (!h->evaluated && !h->began) throw EngineError{HMOGP_E_STATE, "no evaluation to predict from"};
+    if (t < 0 || t >= h->T) throw EngineError{HMOGP_E_INVALID, "task index out of range"};
+    h->predict_log_density(t, Xnew, Ynew, Nnew, lpd_nodes(h->tasks[t].lik, gh_T), lpd, ess);
   });
 }
 

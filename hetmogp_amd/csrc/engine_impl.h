@@ -148,6 +148,9 @@ void weibull_check_rows(const double* y, long long N, double* img);
 void ordinal_row_cuts(const OrdinalTable& tb, const double* y, long long N, double* lo, double* hi);
 // registers (or finds) a table; returns the value to pass as lik_param
 double ordinal_register(int K, const double* edges, double sigma);
+// y of a building block (or new rows of a task) -> device, checked, in the image the row kernels read (abi.hip): [N]; Ordinal [2][N] cut points
+// by `tb`, or by the registry entry `lik_param` names when tb is null; Dirichlet [K][N] log y_k; Weibull [2][N] (log y, delta)
+void upload_y_image(int lik_id, double lik_param, const OrdinalTable* tb, const double* y, long long N, DevBuf& dy);
 
 // Row ranges per weighted-Gram launch: a multiple of 8 (one range per XCD at a time), each >= 32 k-steps of 16 rows,
 // enough blocks (lower tiles x ranges) for >= 8 rounds over the 256 CUs, at most KS_MAX slabs.
@@ -535,6 +538,10 @@ struct hmogp_engine {
   int qu_natgrad_status();
 
   void predict_f(const double* Xnew, long long Nnew, double* m, double* v);
+  // q(f) of one chunk of n <= ws_rows new inputs (host, [n][P]) into dm / dv [n][Df] on the device, enqueued on `st` (predict_f's loop body)
+  void qf_chunk(const double* Xchunk, long long n, DevBuf& dX, DevBuf& dm, DevBuf& dv);
+  // deterministic log predictive density of task t's rows: q(f) stays on the device, only lpd / ess come back; T = nodes per dimension
+  void predict_log_density(int t, const double* Xnew, const double* Ynew, long long Nnew, int T, double* lpd, double* ess);
 
   // ---- likelihood parameters (lik_param.hip) ----
   bool lik_grad_on = false;      // hmogp_lik_grad_enable: persistent

@@ -195,12 +195,40 @@ int hmogp_engine::qu_natgrad_status() {
   return ng_last_taken ? 1 : 0;
 }
 
+void hmogp_engine::qf_chunk(const double* Xchunk, long long n, DevBuf& dX, DevBuf& dm, DevBuf& dv) {
+  const long long MM = (long long)M * M;
+  const int ldz = Q * P;
+  const long long ldn = ws_rows;
+  HIP_TRY(hipMemcpyAsync(dX.p, Xchunk, sizeof(double) * n * P, hipMemcpyHostToDevice, st));
+  if (strict) {
+    RbfBatch rbt;
+    rbt.nq = Q, rbt.var = dvar.d(), rbt.ell = dell.d(), rbt.sZ = P, rbt.sK = ldn * M;
+    launch_rbf(dX.d(), P, n, P, dZ.d(), ldz, M, 0.0, 1.0, Kh.d(), false, st, nullptr, true, &rbt);
+    strict_forward(n, dX.d(), false, false);   // (in the form of the evaluation the prediction is taken from)
+  }
+  for (int q = 0; q < Q && !strict; ++q) {
+    double* kh = Kh.d() + (long long)q * ldn * M;
+    double* pt = Pt.d() + (long long)q * ldn * M;
+    launch_rbf(dX.d(), P, n, P, dZ.d() + q * P, ldz, M, h_var[q], h_ell[q], kh, false, st, nullptr, false);
+    GemmArgs g;
+    g.A = kh, g.lda = M, g.a_kmajor = 0;
+    g.B = Ctri.d() + q * MM, g.ldb = M, g.b_kmajor = 1, g.b_tri = 1;  // variances only: triangular fold of C
+    g.C = pt, g.ldc = M;
+    g.M = (int)n, g.N = M, g.K = M;
+    g.role = 1;
+    g.fs_part = fwdpart.d(), g.fs_a = a.d() + (long long)q * M, g.fs_x = dX.d(), g.fs_z = dZ.d() + q * P;
+    g.fs_ldz = ldz, g.fs_P = P, g.fs_hyper = 0, g.fs_ell = dell.d() + q;
+    g.store_c = 0;
+    const int nparts = launch_gemm_rowpass_or_general(g, st);
+    launch_combine_parts(fwdpart.d(), nparts * ((M + 127) / 128), n, vp.d() + q * ldn, vc.d() + q * ldn, nullptr, nullptr, st);
+  }
+  launch_qf_combine(vp.d(), vc.d(), ldn, n, Q, Df, dW.d(), dkap.d(), dvar.d(), dm.d(), dv.d(), st);
+}
+
 void hmogp_engine::predict_f(const double* Xnew, long long Nnew, double* m, double* v) {
   if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to predict from"};
   if (Nnew < 0 || (Nnew > 0 && (!Xnew || !m || !v))) throw EngineError{HMOGP_E_INVALID, "bad predict arguments"};
   HIP_TRY(hipSetDevice(device));
-  const long long MM = (long long)M * M;
-  const int ldz = Q * P;
   ensure_workspace(std::min(chunk, std::max<long long>(Nnew, 1)));
   ensure_strict_workspace();           // (predictions follow the mode of the evaluation they are taken from)
   const long long ldn = ws_rows;
@@ -208,32 +236,44 @@ void hmogp_engine::predict_f(const double* Xnew, long long Nnew, double* m, doub
   dX.ensure(sizeof(double) * ldn * P), dm.ensure(sizeof(double) * ldn * Df), dv.ensure(sizeof(double) * ldn * Df);
   for (long long r0 = 0; r0 < Nnew; r0 += ldn) {
     const long long n = std::min(ldn, Nnew - r0);
-    HIP_TRY(hipMemcpyAsync(dX.p, Xnew + r0 * P, sizeof(double) * n * P, hipMemcpyHostToDevice, st));
-    if (strict) {
-      RbfBatch rbt;
-      rbt.nq = Q, rbt.var = dvar.d(), rbt.ell = dell.d(), rbt.sZ = P, rbt.sK = ldn * M;
-      launch_rbf(dX.d(), P, n, P, dZ.d(), ldz, M, 0.0, 1.0, Kh.d(), false, st, nullptr, true, &rbt);
-      strict_forward(n, dX.d(), false, false);   // (in the form of the evaluation the prediction is taken from)
-    }
-    for (int q = 0; q < Q && !strict; ++q) {
-      double* kh = Kh.d() + (long long)q * ldn * M;
-      double* pt = Pt.d() + (long long)q * ldn * M;
-      launch_rbf(dX.d(), P, n, P, dZ.d() + q * P, ldz, M, h_var[q], h_ell[q], kh, false, st, nullptr, false);
-      GemmArgs g;
-      g.A = kh, g.lda = M, g.a_kmajor = 0;
-      g.B = Ctri.d() + q * MM, g.ldb = M, g.b_kmajor = 1, g.b_tri = 1;  // variances only: triangular fold of C
-      g.C = pt, g.ldc = M;
-      g.M = (int)n, g.N = M, g.K = M;
-      g.role = 1;
-      g.fs_part = fwdpart.d(), g.fs_a = a.d() + (long long)q * M, g.fs_x = dX.d(), g.fs_z = dZ.d() + q * P;
-      g.fs_ldz = ldz, g.fs_P = P, g.fs_hyper = 0, g.fs_ell = dell.d() + q;
-      g.store_c = 0;
-      const int nparts = launch_gemm_rowpass_or_general(g, st);
-      launch_combine_parts(fwdpart.d(), nparts * ((M + 127) / 128), n, vp.d() + q * ldn, vc.d() + q * ldn, nullptr, nullptr, st);
-    }
-    launch_qf_combine(vp.d(), vc.d(), ldn, n, Q, Df, dW.d(), dkap.d(), dvar.d(), dm.d(), dv.d(), st);
+    qf_chunk(Xnew + r0 * P, n, dX, dm, dv);
     HIP_TRY(hipMemcpyAsync(m + r0 * Df, dm.p, sizeof(double) * n * Df, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(v + r0 * Df, dv.p, sizeof(double) * n * Df, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
+}
+
+// the same chunks as predict_f; the task's columns of q(f) and |v| go straight into the rule's kernel, with the task's CURRENT
+// likelihood parameters (whatever hmogp_set_lik_params last wrote).  Ynew has the layout hmogp_set_task_data takes, and gets its checks.
+void hmogp_engine::predict_log_density(int t, const double* Xnew, const double* Ynew, long long Nnew, int T_, double* lpd, double* ess) {
+  if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to predict from"};
+  if (t < 0 || t >= T) throw EngineError{HMOGP_E_INVALID, "task index out of range"};
+  if (Nnew < 0 || (Nnew > 0 && (!Xnew || !Ynew || !lpd))) throw EngineError{HMOGP_E_INVALID, "bad predict arguments"};
+  if (Nnew == 0) return;
+  const Task& k = tasks[t];
+  HIP_TRY(hipSetDevice(device));
+  DevBuf dy, dl, de;
+  const OrdinalTable* tb = k.lik == HMOGP_LIK_ORDINAL ? &task_table(k) : nullptr;
+  upload_y_image(k.lik, k.param, tb, Ynew, Nnew, dy);      // (checks the rows; throws before anything is launched)
+  dl.ensure(sizeof(double) * Nnew);
+  if (ess) de.ensure(sizeof(double) * Nnew);
+  ensure_workspace(std::min(chunk, std::max<long long>(Nnew, 1)));
+  ensure_strict_workspace();
+  const long long ldn = ws_rows;
+  DevBuf dX, dm, dv;
+  dX.ensure(sizeof(double) * ldn * P), dm.ensure(sizeof(double) * ldn * Df), dv.ensure(sizeof(double) * ldn * Df);
+  for (long long r0 = 0; r0 < Nnew; r0 += ldn) {
+    const long long n = std::min(ldn, Nnew - r0);
+    qf_chunk(Xnew + r0 * P, n, dX, dm, dv);
+    LpdArgs a;
+    a.lik = k.lik, a.J = k.dimf, a.T = T_, a.param = k.qparam, a.N = n;
+    a.y = dy.d() + r0, a.ldy = Nnew;
+    a.m = dm.d() + k.d0, a.v = dv.d() + k.d0, a.ldf = Df, a.absv = true;
+    a.lpd = dl.d() + r0, a.ess = ess ? de.d() + r0 : nullptr;
+    launch_log_predictive_gh(a, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (dX is reused by the next chunk's upload)
+  }
+  HIP_TRY(hipMemcpy(lpd, dl.p, sizeof(double) * Nnew, hipMemcpyDeviceToHost));
+  if (ess) HIP_TRY(hipMemcpy(ess, de.p, sizeof(double) * Nnew, hipMemcpyDeviceToHost));
 }

@@ -1467,3 +1467,16 @@ __device__ __forceinline__ void lik_ordinal_dparam(double lo, double hi, double 
   dhi = a1 / sigma;
   dsig = a2 / sigma;
 }
+
+// ============================================================================ deterministic log predictive density
+// log p(y|f) at one node of the rule for the two families lik_logpdf_sample has no branch for (the reference defines no log_predictive for
+// them).  The families' own links and clips, a = clip(safe_exp(f0), 1e-9, 1e9), b likewise; no division by pi (Q1 is a quirk of the
+// reference's var_exp).  Appended, like DESIGN 9e's functions above, so that nothing in front changes.
+__device__ __forceinline__ double lik_gamma_logpdf(double y, const double* f) {
+  const double a = clip(safe_exp(f[0]), 1e-9, 1e9), b = clip(safe_exp(f[1]), 1e-9, 1e9);
+  return -lgamma(a) + a * log(b) + (a - 1.0) * log(y) - b * y;
+}
+__device__ __forceinline__ double lik_beta_logpdf(double y, const double* f) {
+  const double a = clip(safe_exp(f[0]), 1e-9, 1e9), b = clip(safe_exp(f[1]), 1e-9, 1e9);
+  return (a - 1.0) * log(y) + (b - 1.0) * log(1.0 - y) - (lgamma(a) + lgamma(b) - lgamma(a + b));
+}

@@ -176,6 +176,23 @@ void launch_predictive(int lik, int J, int Jp, double param, int T, long long N,
 // out[n] = -log S + logsumexp_s log p(y_n | f_s), f_s ~ N(m_n, diag v_n): Monte-Carlo log predictive density per row
 void launch_log_predictive(int lik, int J, double param, long long N, int S, unsigned long long seed, const double* y,
                            const double* m, const double* v, double* out, hipStream_t s);
+// Deterministic log predictive density per row (logpred.hip): lpd[n] = log of the Gauss-Hermite tensor rule of p(y_n | f)
+// under q(f) = N(m_n, diag v_n), ess[n] = the rule's effective number of nodes (nullptr: not wanted).  `y` is the image the other
+// building blocks read ([N]; Ordinal [2][ldy] cut points; Weibull [2][ldy]; Dirichlet [K][ldy]); m, v: row n starts at m[n * ldf], so
+// that a task's columns of the engine's [N][Df] q(f) arrays are read in place.  `param`: sigma (Gaussian, Ordinal -- not the table
+// id), nu (Student), K (Categorical, Dirichlet).  T: 10 or 20 nodes per dimension (Categorical, Dirichlet: 10).
+struct LpdArgs {
+  int lik = 0, J = 1, T = 20;
+  double param = 0.0;
+  long long N = 0;
+  const double* y = nullptr;
+  long long ldy = 0;
+  const double *m = nullptr, *v = nullptr;
+  int ldf = 1;
+  bool absv = false;               // take |v| (the engine's q(f) variance, as the facade does)
+  double *lpd = nullptr, *ess = nullptr;
+};
+void launch_log_predictive_gh(const LpdArgs& a, hipStream_t s);
 // Y[n] ~ p(y | F[n]): the reference's `<likelihood>.samples`, one draw per row, counter-based generator
 void launch_sample(int lik, int J, double param, long long N, unsigned long long seed, const double* F, double* Y,
                    hipStream_t s);

@@ -448,6 +448,19 @@ class Engine(object):
         check(lib.hmogp_lik_grad_read(self._h, int(t), _p(g), g.shape[0]), self._h)
         return g
 
+    def predict_log_density(self, t, Xnew, Ynew, gh_T=0):
+        """(lpd, ess) of task t's new rows (hmogp_predict_log_density): q(f) at Xnew stays on the device and feeds the
+        deterministic rule with the task's CURRENT likelihood parameters.  Ynew as set_data takes it for that task."""
+        name, kw = self.specs[int(t)] if 0 <= int(t) < self.T else ("Gaussian", {})
+        Xnew = _f64(Xnew).reshape(-1, self.P)
+        Ynew = _y_rows(name, Ynew, **kw)
+        n = Xnew.shape[0]
+        if Ynew.shape[0] != n:
+            raise _lib.InvalidArgument("predict_log_density: Xnew has %d rows, Ynew %d" % (n, Ynew.shape[0]))
+        lpd, ess = np.zeros(n), np.zeros(n)
+        check(lib.hmogp_predict_log_density(self._h, int(t), _p(Xnew), _p(Ynew), n, int(gh_T), _p(lpd), _p(ess)), self._h)
+        return lpd, ess
+
     def graph_stats(self):
         """(graphs captured, evaluations replayed) of the small-model hipGraph mechanism (hmogp_graph_stats)."""
         cap, rep = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
@@ -598,6 +611,21 @@ def log_predictive_rows(name, y, m, v, num_samples=1000, seed=0, device=None, **
     check(lib.hmogp_log_predictive(device, LIK_IDS[name], lik_param(name, **kw), y.shape[0], int(num_samples), int(seed),
                                    _p(y), _p(m), _p(v), _p(out)))
     return out
+
+
+def log_predictive_density_rows(name, y, m, v, gh_T=0, return_ess=False, device=None, **kw):
+    """Deterministic per-row log predictive density: the log of the Gauss-Hermite tensor rule of p(y_n | f) under
+    q(f) = N(m_n, diag v_n), gh_T nodes per dimension (0: 20, Categorical / Dirichlet 10).  Every family, Gamma and Beta included.
+    return_ess=True: (lpd, ess), ess = the rule's effective number of nodes per row (next to 1: the rule cannot resolve the row)."""
+    device = _resolve_device(device)
+    y, m, v = _y_rows(name, y, **kw), _f64(m), _f64(v)
+    J = lik_dim_f(name, **kw)
+    m, v = m.reshape(-1, J), v.reshape(-1, J)
+    lpd = np.zeros(y.shape[0])
+    ess = np.zeros(y.shape[0]) if return_ess else None
+    check(lib.hmogp_log_predictive_gh(device, LIK_IDS[name], lik_param(name, **kw), int(gh_T), y.shape[0], _p(y), _p(m), _p(v),
+                                      _p(lpd), _p(ess) if return_ess else None))
+    return (lpd, ess) if return_ess else lpd
 
 
 def sample(name, F, seed=0, device=None, **kw):

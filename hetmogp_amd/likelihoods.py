@@ -6,6 +6,38 @@ import numpy as np
 
 from .param import Param
 
+# Rows of the deterministic log predictive density whose effective number of nodes `ess` is below their family's value here are
+# reported by one RuntimeWarning per call: the fixed, prior-centred Gauss-Hermite rule does not resolve a likelihood that much narrower
+# than q(f).  MEASURED, not chosen (tests/test_logpred_cpu.py::test_accuracy_envelope re-measures and prints them; table in DESIGN 9j): per
+# family the largest ess, rounded up to one decimal, among the seeded bulk rows (m in [-3, 3], v in [1e-3, 4]) whose rule differs from the
+# integral itself by more than 1e-2.  One constant for all families does not work: a tensor rule's ess is the product of its dimensions'
+# (a 400-node rule that resolves one dimension and not the other still has ess ~ 10), so the 28.3 of Dirichlet would flag every good
+# one-dimensional row.  Families in which no seeded row misses 1e-2 take the largest value among the families with as many nodes
+# (marked *); Categorical, alone in its class, takes none, and the closed-form Gaussian has ess = +inf.
+LPD_ESS_WARN = {
+    "Gaussian": 0.0, "Bernoulli": 2.4, "Poisson": 2.0, "Exponential": 2.3, "Ordinal": 2.4, "HetGaussian": 2.4,      # Bernoulli *, Ordinal *
+    "Gamma": 11.2, "Beta": 9.0, "Student": 13.8, "Weibull": 14.2, "NegBinomial": 14.2,                              # NegBinomial *
+    "Dirichlet": 28.3, "Categorical": 0.0,
+}
+
+
+def lpd_ess_warn(name, **kw):
+    """The family's LPD_ESS_WARN.  Dirichlet's is measured at K = 3 (10^3 nodes); another K takes the same value per dimension,
+    28.3^(K/3) -- an extrapolation, not a measurement."""
+    c = LPD_ESS_WARN[name]
+    return c ** (int(kw["K"]) / 3.0) if name == "Dirichlet" and "K" in kw else c
+
+
+def warn_low_ess(ess_per_task, specs, what="log_predictive_density"):
+    """One RuntimeWarning naming every task with rows below its family's LPD_ESS_WARN and their number (nothing when there is none).
+    specs: [(family name, kwargs)] per task."""
+    import warnings
+    low = [(t, int(np.sum(np.asarray(e) < lpd_ess_warn(n, **k))), lpd_ess_warn(n, **k)) for t, (e, (n, k)) in enumerate(zip(ess_per_task, specs))]
+    low = ["%d rows of task %d (effective nodes < %.1f)" % (n, t, c) for t, n, c in low if n > 0]
+    if low:
+        warnings.warn("%s: the fixed Gauss-Hermite rule does not resolve %s: the likelihood is much narrower than q(f) there and the "
+                      "values are unreliable" % (what, ", ".join(low)), RuntimeWarning, stacklevel=3)
+
 
 class _Lik(object):
     name = None
@@ -49,6 +81,14 @@ class _Lik(object):
         from .engine import log_predictive_rows
         lp = log_predictive_rows(self.name, Ytest, mu_F_star, v_F_star, num_samples, seed, **self.kwargs())
         return (1.0 / num_samples) * lp.sum()
+
+    def log_predictive_density(self, Ytest, m, v, gh_T=0, return_ess=False):
+        """Deterministic per-row log predictive density (N,) of DESIGN 9j: no sampling, no seed, no 1/num_samples factor; defined
+        for every family.  return_ess=True: (lpd, ess)."""
+        from .engine import log_predictive_density_rows
+        lpd, ess = log_predictive_density_rows(self.name, Ytest, m, v, gh_T=gh_T, return_ess=True, **self.kwargs())
+        warn_low_ess([ess], [(self.name, self.kwargs())])
+        return (lpd, ess) if return_ess else lpd
 
     def predictive(self, m, v, gh_points=None, Y_metadata=None):
         """Predictive mean / variance of y (the reference's `predictive`; Gauss-Hermite order of a fresh instance)."""
@@ -379,6 +419,15 @@ class HetLikelihood(object):
         for t, l in enumerate(self.likelihoods_list):
             logpred += l.log_predictive(Ytest[t], mu_F_star[t], v_F_star[t], num_samples, seed=seed + t)
         return -logpred
+
+    def log_predictive_density(self, Ytest, mu_F, v_F, Y_metadata=None, gh_T=0):
+        """Per-task list of (N_t,) deterministic per-row log predictive densities; one RuntimeWarning per call when some
+        row's effective number of nodes is below LPD_ESS_WARN."""
+        from .engine import log_predictive_density_rows
+        out = [log_predictive_density_rows(l.name, Ytest[t], mu_F[t], v_F[t], gh_T=gh_T, return_ess=True, **l.kwargs())
+               for t, l in enumerate(self.likelihoods_list)]
+        warn_low_ess([o[1] for o in out], self.specs())
+        return [o[0] for o in out]
 
     def var_exp_derivatives(self, Y, mu_F, v_F, Y_metadata):
         out = [l.var_exp_derivatives(Y[t], mu_F[t], v_F[t]) for t, l in enumerate(self.likelihoods_list)]

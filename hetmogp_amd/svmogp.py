@@ -925,9 +925,40 @@ class SVMOGP(object):
         self.parameters_changed()
         return self
 
-    def negative_log_predictive(self, Xtest, Ytest, num_samples=1000, seed=0, route="default"):
+    def log_predictive_density(self, Xtest, Ytest, route="default", gh_T=0, return_ess=False):
+        """Deterministic held-out score: per task an (N_t,) array of per-row log predictive densities, the log of the
+        Gauss-Hermite rule of p(y | f) under q(f) at the test inputs.  Defined for every likelihood (Gamma and Beta included), no
+        seed, no sampling noise.  route="default": q(f) is formed on the device and feeds the rule there with the engine's current
+        likelihood parameters (`hmogp_predict_log_density`); route="reference": q(f) from `_raw_predict_f`, then the stand-alone
+        building block with the likelihoods' current kwargs.  return_ess=True: (lpd list, ess list).  One RuntimeWarning per call
+        when some row's effective number of nodes is below its family's `likelihoods.LPD_ESS_WARN` (the rule cannot resolve such a row)."""
+        from .engine import log_predictive_density_rows
+        from .likelihoods import warn_low_ess
+        if route not in ("default", "reference"):
+            raise ValueError("route must be 'default' or 'reference'")
+        lpd, ess = [], []
+        for t, l in enumerate(self.likelihood.likelihoods_list):
+            if route == "default":
+                self._refresh()
+                a, e = self._engine.predict_log_density(t, np.asarray(Xtest[t], dtype=float).reshape(-1, self.Xdim), Ytest[t], gh_T=gh_T)
+            else:
+                m, v = self._predict_route(Xtest[t], t, route)
+                a, e = log_predictive_density_rows(l.name, Ytest[t], m, v, gh_T=gh_T, return_ess=True, device=self._engine_device(),
+                                                   **l.kwargs())
+            lpd.append(a)
+            ess.append(e)
+        warn_low_ess(ess, self.likelihood.specs())
+        return (lpd, ess) if return_ess else lpd
+
+    def negative_log_predictive(self, Xtest, Ytest, num_samples=1000, seed=0, route="default", method="mc"):
         """svmogp.py:353-370.  q(f) at the test inputs: route="default" from `predict_f`, route="reference" through
-        `_raw_predict_f` as the reference does (see `predictive`)."""
+        `_raw_predict_f` as the reference does (see `predictive`).  method="mc" (default): the reference's Monte-Carlo estimate with
+        its 1/num_samples factor; method="quadrature": minus the sum of all rows of `log_predictive_density` -- deterministic, defined
+        for every likelihood, without that factor; num_samples and seed are ignored."""
+        if method == "quadrature":
+            return -float(sum(np.sum(a) for a in self.log_predictive_density(Xtest, Ytest, route=route)))
+        if method != "mc":
+            raise ValueError("method must be 'mc' or 'quadrature'")
         mu, vv = [], []
         for t in range(len(self.Ymulti_all)):
             m, v = self._predict_route(Xtest[t], t, route)

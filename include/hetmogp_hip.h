@@ -459,6 +459,29 @@ int hmogp_predictive(int32_t device, int32_t lik_id, double lik_param, int32_t g
 int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64_t N, int32_t num_samples, uint64_t seed,
                          const double* y, const double* m, const double* v, double* log_pred);
 
+/* Deterministic log predictive density per test row, for all thirteen families -- Gamma and Beta included, which
+ * hmogp_log_predictive refuses.  For q(f) = N(m_n, diag v_n) over the family's dim_f functions:
+ *   lpd[n] = log sum_nodes (prod_d w_{i_d}) p(y_n | f_node),   f_node,d = m_d + sqrt(2 v_d) x_{i_d},
+ * the Gauss-Hermite tensor rule with gh_T nodes per dimension and weights normalised to sum 1 (gh_T = 0: the default, 20, but 10
+ * for Categorical and Dirichlet, which accept 0 or 10 only; every other family 0, 10 or 20; anything else HMOGP_E_INVALID).
+ * log p(y | f) is what hmogp_log_predictive evaluates per sample; Gamma and Beta: their densities with the families' links and
+ * clips, no division by pi.  Gaussian is the closed form log N(y; m, sigma^2 + v) with the task's sigma (quirk Q6 belongs to the
+ * Monte-Carlo routine only); HetGaussian integrates f0 analytically: gh_T nodes over f1 of log N(y; m0, v0 + safe_exp(f1)).
+ * ess[n] (optional, NULL to skip) = (sum e)^2 / sum e^2 over the nodes' e = (prod w) p: the effective number of nodes.  A value
+ * next to 1 means the likelihood is much narrower than q(f) and the fixed rule cannot resolve it: lpd is then unreliable.
+ * Gaussian: +inf.  A row whose every node has p = 0: lpd = -inf, ess = NaN.  No seed, no sampling noise.
+ * y, its layout per family and its checks are those of hmogp_var_exp / hmogp_log_predictive (Dirichlet [N, K], Weibull [N, 2]);
+ * Gaussian with lik_param <= 0 means sigma = 0.5.  New symbols only: ABI version 8 stays.                                    */
+int hmogp_log_predictive_gh(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, const double* y,
+                            const double* m, const double* v, double* lpd /* [N] */, double* ess /* [N] or NULL */);
+/* The same score for new rows (Xnew [Nnew, P], Ynew in the layout hmogp_set_task_data takes for task t, with its checks) of task t
+ * of an engine: q(f) at Xnew is formed on the device as hmogp_predict_f forms it (same chunks, same strict / default mode), the
+ * task's columns and |v| feed the rule directly with the task's CURRENT likelihood parameters (hmogp_set_lik_params), and only
+ * lpd / ess [Nnew] come back.  HMOGP_E_STATE before the first evaluation; HMOGP_E_INVALID for a t out of range, a bad gh_T, or a
+ * NULL pointer (ess excepted) with Nnew > 0.                                                                                  */
+int hmogp_predict_log_density(hmogp_handle h, int32_t t, const double* Xnew, const double* Ynew, int64_t Nnew, int32_t gh_T,
+                              double* lpd /* [Nnew] */, double* ess /* [Nnew] or NULL */);
+
 /* Data generation on the device: one draw Y[n] ~ p(y | F[n, :]) per row with the link functions and clips of the
  * reference's `<likelihood>.samples` (het_likelihood.py:72-83 -> e.g. gamma.py:43-50, categorical.py:65-75; labels of
  * Categorical are 1..K).  Counter-based generator keyed by (seed, row): reproducible, but a different stream than

@@ -233,27 +233,12 @@ int hmogp_step_finish(hmogp_handle h, hmogp_outputs* out) {
 int hmogp_elbo_grad(hmogp_handle h, const hmogp_params* p, hmogp_outputs* out) {
   if (!h) return HMOGP_E_INVALID;
   return guarded(h, [&] {       // single device, NEVER a collective -- also with a communicator attached (debug / parity calls)
-    static const bool stamps = getenv("HMOGP_HOST_STAMPS") != nullptr;   // host-side timeline of the call (stderr; debugging)
-    static std::chrono::steady_clock::time_point last_ret;
-    const auto t_in = std::chrono::steady_clock::now();
     try {
       h->pending_warm.clear();
       if (h->graphs_broken || !h->graph_step(p, out)) {
         h->begin(p, false);
-        const auto t_b = std::chrono::steady_clock::now();
-        h->finish_enqueue(out);
-        const auto t_e = std::chrono::steady_clock::now();
-        if (stamps) HIP_TRY(hipStreamSynchronize(h->st));
-        const auto t_s = std::chrono::steady_clock::now();
-        h->finish_tail(out);
+        h->finish(out);
         h->mark_warm();
-        if (stamps) {
-          const auto t_r = std::chrono::steady_clock::now();
-          auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-          std::fprintf(stderr, "[hmogp host] outside %.0f us | begin (enqueue) %.0f | finish enqueue %.0f | wait %.0f | tail %.0f\n",
-                       us(last_ret, t_in), us(t_in, t_b), us(t_b, t_e), us(t_e, t_s), us(t_s, t_r));
-          last_ret = t_r;
-        }
       }
     } catch (const hmogp_engine::RetryRegular&) {   // small-model path: a latent needs the jitter ladder
       h->small_veto = true;

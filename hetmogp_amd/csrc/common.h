@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string>
 
 #define HMOGP_WAVE 64
@@ -24,6 +25,15 @@ struct HipError {
     hipError_t _e = (expr);                                    \
     if (_e != hipSuccess) throw HipError{_e, #expr, __FILE__, __LINE__}; \
   } while (0)
+
+// ---- environment switches ----------------------------------------------------------------------------
+// The ONE place the library reads its environment: the numeric value of `name`, `dflt` when it is not set.  The switches are the
+// "Environment variables" list of INTEGRATION.md (tests/test_env_switches_cpu.py holds the two together); callers keep the value
+// in a function-local static, so the environment is read once per process.
+inline double env_num(const char* name, double dflt) {
+  const char* e = getenv(name);
+  return e ? atof(e) : dflt;
+}
 
 // ---- wave-level reductions (64 lanes, shuffles -- no LDS) ---------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
@@ -71,7 +81,6 @@ struct GemmArgs {
   long long sSplit = 0;
   int a_kmajor = 0, b_kmajor = 1;
   int lower_only = 0;
-  int diag_balance = 1;  // role 2: balance the diagonal tiles' sub-tiles over the physical SIMDs of the CU (gemm_rowpass.hip)
   int role = 0;  // 0 generic, 1 forward contraction, 2 weighted Gram (names the kernel instantiation for profiles)
   // role 1 only -- row statistics fused into the epilogue while the P~ tile is still in registers (replaces a separate
   // pass over K^ and P~):  for every row n of the tile and this block's 128 columns j
@@ -115,13 +124,12 @@ void launch_gemm_f64(const GemmArgs& g, hipStream_t stream);
 // The two row-pass contractions (role 1 / 2) as specialised 8-wave kernels (gemm_rowpass.hip) when the shape allows it,
 // else the general kernel.  Returns the number of fused-row-statistics partials per 128-column tile the role-1 kernel
 // wrote (what launch_combine_parts has to sum): 4 (specialised) or 2 (general).
-bool gemm_rowpass_eligible(const GemmArgs& g);
+bool gemm_rowpass_eligible(const GemmArgs& g);   // will launch_gemm_rowpass_or_general use the specialised kernel for g?
 void launch_gemm_rowpass(const GemmArgs& g, hipStream_t stream);
 int launch_gemm_rowpass_or_general(const GemmArgs& g, hipStream_t stream);
-bool gemm_rowpass_would_take(const GemmArgs& g);   // will launch_gemm_rowpass_or_general use the specialised kernel for g?
 constexpr int GEMM_MAX_FWD_PARTS = 4;
 // 64 x 64-tile kernel for the replicated M x M products (gemm_small.hip); launch_gemm_f64 picks it when the 128-tile grid
-// would leave the device under-filled (env HMOGP_SMALL_GEMM=0 disables it).
+// would leave the device under-filled.
 bool gemm_small_eligible(const GemmArgs& g);
 void launch_gemm_small(const GemmArgs& g, hipStream_t stream);
 

@@ -25,7 +25,7 @@ hipEvent_t hmogp_engine::new_event() {
 }
 
 void hmogp_engine::collect_spans() {
-  static const bool dbg = getenv("HMOGP_DEBUG_TIMELINE") != nullptr;   // start / end of every span relative to the step's start
+  static const bool dbg = env_num("HMOGP_DEBUG_TIMELINE", 0) != 0;   // =1: start / end of every span relative to the step's start
   for (auto& s : spans) {
     float f = 0.f;
     if (hipEventElapsedTime(&f, s.a, s.b) == hipSuccess) ms[s.cat] += f;
@@ -89,35 +89,7 @@ void hmogp_engine::init(const hmogp_config* c) {
     int lo = 0, hi = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
     HIP_TRY(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, hi));
-    // HMOGP_ST2_CUS=<n> (experiment): give the second stream a CU mask of n of the device's CUs instead of a low
-    // priority, so that the latency-bound chains of the other streams always find free CUs beside its HBM-bound work
-    const char* cus_env = getenv("HMOGP_ST2_CUS");
-    int cus = cus_env ? atoi(cus_env) : 0;
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (cus > 0 && cus < prop.multiProcessorCount) {
-      std::vector<uint32_t> mask((prop.multiProcessorCount + 31) / 32, 0u);
-      for (int i = 0; i < cus; ++i) mask[i / 32] |= 1u << (i % 32);
-      if (hipExtStreamCreateWithCUMask(&st2, (uint32_t)mask.size(), mask.data()) != hipSuccess) st2 = nullptr;
-    }
-    // HMOGP_ST2_FREE=<n> with HMOGP_ST2_LAYOUT=0|1 (experiment): leave n CUs of EVERY XCD out of the second stream's mask --
-    // a mask that drops whole XCDs unbalances kernels whose blocks are dealt round-robin over the XCDs.  Layout 0: mask bit
-    // i = CU i % 32 of XCD i / 32; layout 1: bit i = CU i / 8 of XCD i % 8.
-    const char* free_env = getenv("HMOGP_ST2_FREE");
-    const int nfree = free_env ? atoi(free_env) : 0;
-    if (!st2 && nfree > 0 && nfree < 32 && prop.multiProcessorCount == 256) {
-      const char* lay = getenv("HMOGP_ST2_LAYOUT");
-      const int layout = lay ? atoi(lay) : 1;
-      st2_masked = true;
-      std::vector<uint32_t> mask(8, 0xFFFFFFFFu);
-      for (int x = 0; x < 8; ++x)
-        for (int c = 32 - nfree; c < 32; ++c) {
-          const int bit = layout == 0 ? x * 32 + c : c * 8 + x;
-          mask[bit / 32] &= ~(1u << (bit % 32));
-        }
-      if (hipExtStreamCreateWithCUMask(&st2, (uint32_t)mask.size(), mask.data()) != hipSuccess) st2 = nullptr, st2_masked = false;
-    }
-    if (!st2) HIP_TRY(hipStreamCreateWithPriority(&st2, hipStreamNonBlocking, lo));
+    HIP_TRY(hipStreamCreateWithPriority(&st2, hipStreamNonBlocking, lo));
     HIP_TRY(hipStreamCreateWithPriority(&st3, hipStreamNonBlocking, hi));
     st2_own = st2, st3_own = st3;
   }
@@ -356,10 +328,6 @@ void hmogp_engine::upload_params(const hmogp_params* p, bool enqueue) {
 }
 
 void hmogp_engine::decide_mode(const hmogp_params* p) {
-  static const int small_env = [] {   // HMOGP_SMALL_MODE=0|1: force the small-problem mode off / on (A/B runs)
-    const char* e = getenv("HMOGP_SMALL_MODE");
-    return e ? atoi(e) : -1;
-  }();
   long long rows_eval = 0;
   for (int t = 0; t < T && p; ++t) {
     const long long b = p->row_begin ? p->row_begin[t] : 0, e = p->row_end ? p->row_end[t] : tasks[t].N;
@@ -374,7 +342,7 @@ void hmogp_engine::decide_mode(const hmogp_params* p) {
   strict = strict_cfg || (p && (p->eval_flags & HMOGP_EVAL_STRICT_QF) != 0);
   skip_g_L = p && (p->eval_flags & HMOGP_EVAL_NO_G_L) != 0;
   if (strict && use_windows) throw EngineError{HMOGP_E_INVALID, "strict q(f) and HMOGP_CFG_EXACT_ZERO_WINDOWS exclude each other"};
-  const bool want_small = !no_small && !strict && (small_env >= 0 ? small_env != 0 : (M <= 128 && rows_eval <= 65536 && !use_windows && !st2_masked));
+  const bool want_small = !no_small && !strict && M <= 128 && rows_eval <= 65536 && !use_windows;
   if (want_small != small_mode) {     // (rare: drain the queues the previous evaluations used before re-wiring them)
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipStreamSynchronize(st2_own));
@@ -383,21 +351,12 @@ void hmogp_engine::decide_mode(const hmogp_params* p) {
     st2 = small_mode ? st : st2_own;
     st3 = small_mode ? st : st3_own;
   }
-  static const int path_env = [] {   // HMOGP_SMALL_PATH=0: keep the regular kernels in small-problem mode (A/B runs)
-    const char* e = getenv("HMOGP_SMALL_PATH");
-    return e ? atoi(e) : 1;
-  }();
   // (a SHARDED step -- hmogp_elbo_grad_sharded, or the split form hmogp_step_begin ... hmogp_step_finish whose bundle the caller
   //  exchanges with whatever it has: the library's communicator, torch.distributed, MPI -- must not choose its path from this
   //  rank's row count: every rank takes the regular kernels, so that the replicated M x M algebra, and with it the never
   //  re-synchronised resident q(u) replicas, round alike on all ranks.  ADVICE r4.  Plain hmogp_elbo_grad is unaffected.)
-  small_path = small_mode && M <= HMOGP_SMALL_M && path_env != 0 && !small_veto && !sharded_call;
+  small_path = small_mode && M <= HMOGP_SMALL_M && !small_veto && !sharded_call;
   small_info_pending = false;
-  static const int rows_env = [] {   // HMOGP_SMALL_ROWS=0: the regular row-pass kernels behind the fused M x M kernels (A/B runs)
-    const char* e = getenv("HMOGP_SMALL_ROWS");
-    return e ? atoi(e) : 1;
-  }();
-  small_rows = small_path && rows_env != 0;
 }
 
 void hmogp_engine::begin(const hmogp_params* p, bool sync, bool will_exchange) {
@@ -569,14 +528,8 @@ void hmogp_engine::finish_enqueue(hmogp_outputs* out) {
     // [r5] gathered STRAIGHT into the page-locked host block (its device-side address), like the small-model path: the separate
     // D2H copy command behind the gather kernel started 240-390 us after it (rocprofv3 timelines of H and C3: the copy waited
     // for the 12.6 MB g_L_u transfer of the other stream to drain) -- 5 % of a minibatch step for 10 KB of results.
-    static const bool direct = [] {   // HMOGP_GATHER_DIRECT=0: gather into HBM + hipMemcpyAsync as before (A/B runs)
-      const char* e = getenv("HMOGP_GATHER_DIRECT");
-      return !(e && e[0] == '0');
-    }();
-    double* d = direct ? hstage_dev : dstage.d();
     launch_gather_small(stats.d(), (long long)n_hg, klout.d(), (long long)n_kl, per_q, oDZ, per_q - oDZ, Q, rowout.d(),
-                        (long long)n_row, d, st);
-    if (!direct) HIP_TRY(hipMemcpyAsync(hstage, d, sizeof(double) * n_stage, hipMemcpyDeviceToHost, st));
+                        (long long)n_row, hstage_dev, st);
   }
   if (out->dL_dS) HIP_TRY(hipMemcpyAsync(out->dL_dS, dLdS.p, sizeof(double) * MM * Q, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipEventRecord(ev_fin1, st));

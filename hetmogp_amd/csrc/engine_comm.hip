@@ -62,10 +62,7 @@ void hmogp_engine::comm_abort() {
 }
 
 void hmogp_engine::wait_exchanged() {
-  static const double limit_s = [] {
-    const char* e = getenv("HMOGP_COMM_TIMEOUT_S");
-    return e ? atof(e) : 600.0;
-  }();
+  static const double limit_s = env_num("HMOGP_COMM_TIMEOUT_S", 600.0);
   RcclApi& r = rccl();
   const auto t0 = std::chrono::steady_clock::now();
   for (long long spin = 0;; ++spin) {

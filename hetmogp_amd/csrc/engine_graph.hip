@@ -19,10 +19,7 @@ std::vector<long long> hmogp_engine::graph_key(const hmogp_params* p) const {
 }
 
 bool hmogp_engine::graph_step(const hmogp_params* p, hmogp_outputs* out) {
-  static const bool enabled = [] {   // HMOGP_SMALL_GRAPH=0: no graphs (A/B runs)
-    const char* e = getenv("HMOGP_SMALL_GRAPH");
-    return !(e && e[0] == '0');
-  }();
+  static const bool enabled = env_num("HMOGP_SMALL_GRAPH", 1) != 0;   // HMOGP_SMALL_GRAPH=0: no graphs
   if (!enabled || !p || !out || out->dL_dS || small_veto || comm) return false;
   HIP_TRY(hipSetDevice(device));
   sharded_call = false;   // (only plain hmogp_elbo_grad comes here; a stale `true` from an earlier hmogp_step_begin / sharded step made

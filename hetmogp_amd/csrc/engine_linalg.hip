@@ -111,11 +111,6 @@ void ordinal_row_cuts(const OrdinalTable& tb, const double* y, long long N, doub
 }
 
 int gram_ksplit(long long n, int M) {
-  static const int forced = [] {   // HMOGP_GRAM_KSPLIT=<row ranges> (experiments; profiles/r03_gram_ksplit.txt: flat)
-    const char* e = getenv("HMOGP_GRAM_KSPLIT");
-    return e ? atoi(e) : 0;
-  }();
-  if (forced > 0) return (int)std::max<long long>(1, std::min<long long>(forced, (n + 15) / 16));
   const int tiles = (M + 127) / 128, ntl = tiles * (tiles + 1) / 2;
   const long long ksteps = (n + 15) / 16;
   // enough blocks to fill the chip several times over, and row ranges of at most ~8192 rows (the tiles of one range drift
@@ -225,7 +220,7 @@ bool potrs_rows_inplace(double* V, long long sV, const double* Luu, long long sL
   // [r6] ONE launch per 128-column block and direction (trsm_panel.hip): the block's long-K update and the substitution inside it
   // with the 128 x 128 tile in the accumulators throughout -- the right-hand sides are read once (from `Vsrc` by the forward
   // solve: no copy) and written once per solve, and the backward solve's epilogue forms the row statistics of A on the way out.
-  // 16 launches at M = 1024 where round 5 needed 80; the round-5 path below stays for ragged M, short passes and A/B runs.
+  // 16 launches at M = 1024 where round 5 needed 80; the round-5 path below stays for ragged M and short passes.
   if (sym && rdiag) {
     TrsmPanelArgs pa;
     pa.V = V, pa.sV = sV, pa.ldv = M, pa.Lsym = Lsym, pa.sL = sL, pa.ldl = M, pa.rdiag = rdiag, pa.sR = M, pa.n = n, pa.M = M, pa.Q = Q;
@@ -260,25 +255,17 @@ bool potrs_rows_inplace(double* V, long long sV, const double* Luu, long long sL
   // 128-column block (strict forward at the headline size: 568 ms one-level, 337 ms two-level).
   // [r5] inside a 128-column block the short updates ride in the substitution launches (right-looking, on the matrix cores, x taken
   // from LDS: trsm_diag_kernel) where the shape allows it: 7 launches and ~740 column passes over HBM per block become 4 and 640
-  static const bool fuse_env = [] {   // HMOGP_TRSM_FUSE=0: separate 32-column GEMM updates (A/B runs)
-    const char* e = getenv("HMOGP_TRSM_FUSE");
-    return !(e && e[0] == '0');
-  }();
-  const bool fuse = fuse_env && trsm_diag_can_fuse(V, sV, M);
+  const bool fuse = trsm_diag_can_fuse(V, sV, M);
   constexpr int NB = 128;
   // first touch instead of a copy: every 128-column update of the forward solve must be taken by the specialised kernel (the
   // general one has no separate source) and every block's first substitution launch by the row-coalesced one
   bool first_touch = false;
   if (Vsrc && fwd) {
-    static const bool ft_env = [] {   // HMOGP_STRICT_FIRST_TOUCH=0: copy the right-hand sides in front of the solve (A/B runs)
-      const char* e = getenv("HMOGP_STRICT_FIRST_TOUCH");
-      return !(e && e[0] == '0');
-    }();
-    first_touch = ft_env && fuse && sym && (M % NB) == 0 && (reinterpret_cast<uintptr_t>(Vsrc) & 15) == 0;
+    first_touch = fuse && sym && (M % NB) == 0 && (reinterpret_cast<uintptr_t>(Vsrc) & 15) == 0;
     for (int J0 = NB; first_touch && J0 < M; J0 += NB) {
       GemmArgs g = update_args(J0, NB, 0, J0, Lsym + J0, 1);
       g.c_src = Vsrc + J0;
-      first_touch = gemm_rowpass_would_take(g);
+      first_touch = gemm_rowpass_eligible(g);
     }
     if (!first_touch)
       for (int q = 0; q < Q; ++q)

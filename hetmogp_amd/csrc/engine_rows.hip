@@ -13,8 +13,7 @@ void hmogp_engine::u_algebra_small() {
   //  parameter block, and zeroes the statistic bundle the row pass accumulates into)
   if (!pools.empty()) {
     stage_pool_inputs(pools[0], st);
-    if (!small_rows) kuf_pool(pools[0], st);      // (the fused forward kernel builds K^ itself)
-    kuf_prefetched = true;
+    kuf_prefetched = true;                        // (no K_uf launch: the fused forward kernel builds K^ itself)
     HIP_TRY(hipEventRecord(ev_kuf, st));
   }
   SmallU u;
@@ -166,10 +165,8 @@ void hmogp_engine::u_algebra() {
     for (int q = 0; q < Q; ++q) cond_two = cond_two || !(h_cond[q] <= 1e6);
   }
   if (strict) {
-    static const int force = [] {   // HMOGP_STRICT_FORM=1 | 2: force the one-solve / two-solve form (A/B runs)
-      const char* e = getenv("HMOGP_STRICT_FORM");
-      return e ? atoi(e) : 0;
-    }();
+    // HMOGP_STRICT_FORM=1 | 2: force the one-solve / two-solve form (tools/forms_vs_literal.py, tools/strict_ab.py: the evidence below)
+    static const int force = (int)env_num("HMOGP_STRICT_FORM", 0);
     // The one-solve form up to the condition estimate 1e6, the two-solve form beyond.  P~ = A (S Kuu^-1 - I) -- needed by the K_uf-side
     // gradients only -- is the one product whose one-solve form X (Luu^-1 (S Kuu^-1 - I)) drifts from the two-solve one as K_uu
     // degrades: form against form at M = 1024 (tools/strict_ab.py ... forms) the worst element-wise excess over the 1e-5 criterion is
@@ -231,11 +228,7 @@ void hmogp_engine::kuf_pool(const std::vector<Seg>& pl, hipStream_t stream, size
     // On the side stream the construction is cut into launches of KUF_CHUNK_ROWS rows (~70 us each): a kernel that fills
     // every CU for a millisecond stalls every launch of the latency-bound chains on the other streams until it has
     // drained (stream priorities notwithstanding); between short launches they slip in.
-    static const long long chunk_env = [] {   // HMOGP_KUF_CHUNK=<rows per launch on the side stream> (experiment)
-      const char* e = getenv("HMOGP_KUF_CHUNK");
-      return e ? atoll(e) : 0LL;
-    }();
-    const long long step = (stream != st && !use_windows) ? (chunk_env > 0 ? chunk_env : (st2_masked ? 100000LL : KUF_CHUNK_ROWS)) : sg.n;
+    const long long step = (stream != st && !use_windows) ? KUF_CHUNK_ROWS : sg.n;
     for (long long r = 0; r < sg.n; r += step)
       launch_rbf(Xs + r * P, P, std::min(step, sg.n - r), P, dZ.d(), ldz, M, 0.0, 1.0, Kh.d() + (sg.off + r) * M, false, stream,
                  rw, strict, &rbt);   // (strict q(f): GPy's rounding order, sqrt and divide included)
@@ -286,14 +279,10 @@ void hmogp_engine::strict_forward(long long n, const double* X, bool grads, bool
   ts.part = trsmpart.d(), ts.sPart = 8 * ldn, ts.ld = ldn;
   if (strict_two) ts.K = Kh.d(), ts.vec = dmu.d(), ts.vecB = 1, ts.vecS = Q;        // two-solve form: p = A m, rowsum(A .* K^)
   else ts.K = nullptr, ts.vec = w3.d(), ts.vecB = M, ts.vecS = 1;                    // one-solve form: p = X w3, rowsum(X .* X)
-  static const bool ts_env = [] {   // HMOGP_TRSM_STATS=0: the statistics by strict_rowstats_kernel (A/B runs)
-    const char* e = getenv("HMOGP_TRSM_STATS");
-    return !(e && e[0] == '0');
-  }();
   bool stats_fused = false;
   {
     Scope sc(this, CAT_TRSM, (strict_two ? 2 : 1) * ((M + 127) / 128));
-    stats_fused = potrs_rows_inplace(Ah.d(), sK, Luu.d(), MM, M, n, Q, st, Lsy.d(), Kh.d(), rdiag.d(), ts_env ? &ts : nullptr,
+    stats_fused = potrs_rows_inplace(Ah.d(), sK, Luu.d(), MM, M, n, Q, st, Lsy.d(), Kh.d(), rdiag.d(), &ts,
                                      strict_two ? 3 : 1, lsym_valid);
   }
   const double* Bt = strict_two ? L.d() : Wq.d();       // right factor of T:  A L_q  |  X (Luu^-1 L_q)      (both lower triangular)
@@ -312,11 +301,7 @@ void hmogp_engine::strict_forward(long long n, const double* X, bool grads, bool
     g.role = 1;
     const int tiles = (M + 127) / 128;
     g.fs_part = fwdpart.d(), g.fs_sPart = 4LL * FWD_PARTS * tiles * ldn, g.fs_sq = 1, g.store_c = 0;
-    static const bool t2_env = [] {   // HMOGP_STRICT_T2=0: T stored and squared by strict_rowstats_kernel (A/B runs)
-      const char* e = getenv("HMOGP_STRICT_T2");
-      return !(e && e[0] == '0');
-    }();
-    if (t2_env && gemm_rowpass_would_take(g)) {
+    if (gemm_rowpass_eligible(g)) {
       const int nparts = launch_gemm_rowpass_or_general(g, st);
       launch_combine_parts(fwdpart.d(), nparts * tiles, n, nullptr, vct.d(), nullptr, nullptr, st, Q, g.fs_sPart, ldn);
       t2_fused = true;
@@ -345,10 +330,6 @@ void hmogp_engine::strict_forward(long long n, const double* X, bool grads, bool
   // read through `fs_k` (K^ is not this product's A operand), and the r2-weighted statistic of the lengthscale gradient comes
   // from the column statistics (colstats<STRICT, SL>: GPy's r2 form): no pass of strict_rowstats_kernel over K^ and P~
   // (39 GB, 8.7 ms at the headline size).  `hyper` then only says that colstats carries the weight.
-  static const bool p1_env = [] {   // HMOGP_STRICT_P1=0: phase 1 by strict_rowstats_kernel as in round 5 (pg / cg only; A/B runs)
-    const char* e = getenv("HMOGP_STRICT_P1");
-    return !(e && e[0] == '0');
-  }();
   {
     GemmArgs g;
     g.A = Ah.d(), g.lda = M, g.a_kmajor = 0, g.sA = sK;
@@ -359,7 +340,7 @@ void hmogp_engine::strict_forward(long long n, const double* X, bool grads, bool
     g.role = 1;
     const int tiles = (M + 127) / 128;
     g.fs_part = fwdpart.d(), g.fs_sPart = 4LL * FWD_PARTS * tiles * ldn, g.fs_a = a.d(), g.fs_sA = M, g.fs_k = Kh.d();
-    if (p1_env && gemm_rowpass_would_take(g)) {
+    if (gemm_rowpass_eligible(g)) {
       {
         Scope sc(this, CAT_FWD, 1);
         launch_gemm_rowpass_or_general(g, st);
@@ -405,18 +386,14 @@ void hmogp_engine::row_pass() {
       if (!prefetched) stage_pool_inputs(pl, st);
       X = Xws.d();
     }
-    if (!prefetched && !small_rows) kuf_pool(pl, st);
+    if (!prefetched && !small_path) kuf_pool(pl, st);
     // Forward contraction for all latents (batched), row statistics fused into its epilogue; P~ itself is only stored
     // when the Z gradient (its one remaining consumer, colstats) is requested.  One launch per pool.
     const long long sPart = 4LL * FWD_PARTS * tiles * ldn;
     const long long clen = (long long)M * (2 + P);          // one column-statistics slab: [ r (M) | dZ (M*P) | s2 (M) ]
     // [r5] the r2-weighted statistic of the lengthscale gradient comes from the column statistics (E and x - z are in hand there),
     // not from two more row statistics of the forward epilogue; strict q(f) keeps its own (strict_rowstats_kernel, GPy's r2 form)
-    static const bool col_sl_env = [] {   // HMOGP_COL_SL=0 (TIMING ONLY: sl is then missing from the lengthscale gradient)
-      const char* e = getenv("HMOGP_COL_SL");
-      return !(e && e[0] == '0');
-    }();
-    const bool col_sl = want_hyper && !small_rows && col_sl_env;     // ([r6] strict q(f) too: colstats<STRICT> weights with GPy's r2 form)
+    const bool col_sl = want_hyper && !small_path;     // ([r6] strict q(f) too: colstats<STRICT> weights with GPy's r2 form)
     // slabs of the column statistics: 256-row splits
     const long long csplit = col_split(n);
     const long long nsp = (n + csplit - 1) / csplit;        // slabs of the column statistics
@@ -473,21 +450,18 @@ void hmogp_engine::row_pass() {
       // 26.2 ms instead of 42.7 at the headline size, the Gram unchanged at 39.7).  The cap is no longer proportional to 1 / M:
       // 256 blocks at M <= 512 (Gram 10.7 ms, column statistics 10.5: 33.5 ms per step instead of 34.9), 192 at M >= 1024
       // (profiles/r05_colstats_cap.txt).
-      static const int cap_env = [] {   // HMOGP_COLSTATS_CAP=<blocks in flight> (0 = one block per row split)
-        const char* e = getenv("HMOGP_COLSTATS_CAP");
-        return e ? atoi(e) : -1;
-      }();
       // (exact-zero windows: the banded Gram is short; the cap was sized for the dense one)
       // (P > 1: more arithmetic per byte -- a block streams 4.8 instead of 6.3 GB/s at P = 2 -- so proportionally more of them)
       // (strict q(f): the kernel streams a third matrix -- 256 blocks keep it as long as the Gram of A: 313.5 -> 310.7 ms at H)
-      const int cap = cap_env >= 0 ? cap_env : (use_windows ? 0 : (int)(std::min(256.0, std::max(strict ? 256.0 : 192.0, 131072.0 / std::max(1, M))) * (1.0 + 0.35 * (P - 1))));
+      // (cap 0 = one block per row split)
+      const int cap = use_windows ? 0 : (int)(std::min(256.0, std::max(strict ? 256.0 : 192.0, 131072.0 / std::max(1, M))) * (1.0 + 0.35 * (P - 1)));
       launch_colstats(Kh.d() + off * M, Pt.d() + off * M, a.d(), valpha.d() + off, valpha0.d() + off, vbeta0.d() + off,
                       X + off * P, P, dZ.d(), ldz, rows, M, (int)csplit, want_z, colpart.d() + slab_first * clen, st2, cw, &cb, cap,
                       strict ? Ah.d() + off * M : nullptr, col_sl ? dell.d() : nullptr);
     };
 
     SmallRows sr;
-    if (small_rows) {
+    if (small_path) {
       const long long nblk = (n + 63) / 64, slab_q = (long long)M * M + M + (long long)M * P;
       sr.M = M, sr.Q = Q, sr.P = P, sr.ldz = ldz, sr.hyper = want_hyper ? 1 : 0, sr.want_z = want_z ? 1 : 0, sr.n = n, sr.ldn = ldn;
       sr.X = X, sr.Z = dZ.d(), sr.var = dvar.d(), sr.ell = dell.d(), sr.C = C.d(), sr.a = a.d();
@@ -538,12 +512,8 @@ void hmogp_engine::row_pass() {
     // [r5] ... and on the regular path too where the pool is SHORT (minibatches, rank shares: four launches of a few dozen blocks
     // + four reductions were 0.17 ms between the forward and the Gram of an 8192-row step) and its likelihood set has an
     // instantiation of its own; the full-batch sizes keep one launch per task (each with its own register allocation)
-    static const bool qm_regular_env = [] {   // HMOGP_QUAD_MULTI_REGULAR=0: one quadrature launch per task on the regular path
-      const char* e = getenv("HMOGP_QUAD_MULTI_REGULAR");
-      return !(e && e[0] == '0');
-    }();
-    bool quad_multi = small_rows && (int)pl.size() <= HMOGP_QUAD_MULTI && qblocks <= 2048;
-    const bool qm_regular = !small_rows && !strict && qm_regular_env && pl.size() >= 2 && (int)pl.size() <= HMOGP_QUAD_MULTI &&
+    bool quad_multi = small_path && (int)pl.size() <= HMOGP_QUAD_MULTI && qblocks <= 2048;
+    const bool qm_regular = !small_path && !strict && pl.size() >= 2 && (int)pl.size() <= HMOGP_QUAD_MULTI &&
                             qblocks <= 2048;
     if (quad_multi || qm_regular) {
       QuadMulti qm;
@@ -583,7 +553,7 @@ void hmogp_engine::row_pass() {
     // column statistics of segment i beside the forward contraction of segment i + 1 -- the Gram gains 4.0 ms, the
     // forward contractions lose 5.7 ms: an HBM-saturating kernel costs an FP64-MFMA GEMM beside it about its own
     // stand-alone time either way.)
-    if (small_rows) {
+    if (small_path) {
       Scope sc(this, CAT_GRAM, 2);
       launch_small_bwd(sr, st, quad_multi ? &qred : nullptr);   // H_q, r_q, dZ_q: block partials + their ordered sum into the bundle
       continue;
@@ -604,11 +574,6 @@ void hmogp_engine::row_pass() {
       g.lower_only = 1;
       g.ksplit = ksplit, g.sSplit = MM;
       g.role = 2;
-      static const int bal = [] {   // HMOGP_DIAG_BALANCE=0: static sub-tile assignment on the diagonal tiles (A/B runs)
-        const char* e = getenv("HMOGP_DIAG_BALANCE");
-        return e ? atoi(e) : 1;
-      }();
-      g.diag_balance = bal;
       g.win = cw, g.win_stride = 2 * ncb;
       {
         Scope sc(this, CAT_GRAM, 1);

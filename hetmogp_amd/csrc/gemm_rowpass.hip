@@ -435,7 +435,7 @@ __global__ __launch_bounds__(NT, 4) void rowpass_gemm_kernel(GemmArgs g, int til
   __shared__ __attribute__((aligned(16))) Tile lds;
   __shared__ __attribute__((aligned(16))) double epi_a[ROLE == 1 ? 128 : 2];
   __shared__ int hwinfo[ROLE == 2 ? 16 : 1];
-  rowpass_block<ROLE, false>(g, tiles_n, ntiles, lds, epi_a, (ROLE == 2 && g.diag_balance) ? hwinfo : nullptr);
+  rowpass_block<ROLE, false>(g, tiles_n, ntiles, lds, epi_a, ROLE == 2 ? hwinfo : nullptr);
 }
 // the forward contraction against the triangular fold of C, two column tiles per block (see rowpass_block)
 __global__ __launch_bounds__(NT, 4) void rowpass_fold_pair_kernel(GemmArgs g, int tiles_n, int ntiles) {
@@ -489,20 +489,11 @@ void launch_gemm_rowpass(const GemmArgs& g_in, hipStream_t stream) {
   }
 }
 
-static bool rowpass_enabled() {
-  static const bool enabled = [] {   // HMOGP_ROWPASS=0 forces the general kernel (A/B measurements)
-    const char* e = getenv("HMOGP_ROWPASS");
-    return !(e && e[0] == '0');
-  }();
-  return enabled;
-}
-bool gemm_rowpass_would_take(const GemmArgs& g) { return rowpass_enabled() && gemm_rowpass_eligible(g); }
-
 int launch_gemm_rowpass_or_general(const GemmArgs& g, hipStream_t stream) {
-  const bool enabled = rowpass_enabled();
-  if ((g.fs_sq || g.fs_k) && !(enabled && gemm_rowpass_eligible(g)))
+  const bool eligible = gemm_rowpass_eligible(g);
+  if ((g.fs_sq || g.fs_k) && !eligible)
     throw HipError{hipErrorInvalidValue, "fs_sq / fs_k are features of the specialised forward kernel only", __FILE__, __LINE__};
-  if (enabled && gemm_rowpass_eligible(g)) {
+  if (eligible) {
     launch_gemm_rowpass(g, stream);
     return NWN;
   }

@@ -444,15 +444,11 @@ void launch_potrf_batched(double* A, int Q, int M, int* d_info, double* scr, hip
   for (int pnl = panel_begin; pnl < panel_end; ++pnl) {
     const int j = pnl * NB;
     const int rem = M - j - std::min(NB, M - j);
-    static const int forced = [] {   // HMOGP_POTRF_TILE=64|128: force one tile size (A/B runs)
-      const char* e = getenv("HMOGP_POTRF_TILE");
-      return e ? atoi(e) : 0;
-    }();
     // 64 x 64 tiles while they give at most two blocks per CU (block 0's critical path 19 -> 10.4 us, phase stamps in
     // profiles/r04_potrf_phases.txt; 0.608 -> 0.546 ms at M = 1024, Q = 3); with more blocks than that the redundant diagonal-
     // block loads and panel solves of every block cost more than the shorter tile update gains (M = 2048: 1.53 -> 1.79 ms).
     const int T64 = (rem + 63) / 64;
-    const int ts = forced == 64 || forced == 128 ? forced : ((long long)T64 * (T64 + 1) / 2 * Q <= 512 ? 64 : 128);
+    const int ts = (long long)T64 * (T64 + 1) / 2 * Q <= 512 ? 64 : 128;
     const int T = (rem + ts - 1) / ts;
     const dim3 grid(std::max(1, T * (T + 1) / 2) + (rem > 0 ? 1 : 0), Q);
     if (ts == 128)

@@ -17,7 +17,7 @@
 // regular path, which owns the ladder.  Arithmetic: plain FP64 FMAs on 4 x 4 register micro-tiles (a 64^3 product is
 // ~4 us on one CU; MFMA tiles would not be faster at one block per latent) -- results agree with the blocked kernels to rounding.
 // The sequential chains (Cholesky, triangular inverses) run on single waves with the matrix in registers: sm_potrf_regs /
-// sm_trtri_regs; the LDS-resident versions stay for A/B runs (HMOGP_SMALL_REGS=0).  DESIGN.md 11e has the step-by-step timings.
+// sm_trtri_regs.  DESIGN.md 11e has the step-by-step timings.
 #include <cstdio>
 #include "common.h"
 #include "post.h"
@@ -67,7 +67,7 @@ __device__ __forceinline__ void sm_gemm_fma(const double* __restrict__ A, const 
 // The same product on the matrix cores: four waves, each a 32 x 32 quadrant = 2 x 2 tiles of v_mfma_f64_16x16x4_f64 (A fragment:
 // row = lane & 15, k = lane >> 4; B fragment: k = lane >> 4, column = lane & 15; D: column = lane & 15, row = (lane >> 4) + 4 reg --
 // gemm_small.hip's conventions).  k beyond M would bring in the buffers' garbage: those fragment entries are zeros.  Triangular
-// k-trimming per quadrant (the operands carry explicit zeros there).  Measured at M = 50 (u_small_kernel's phase stamps): 4.4 us per
+// k-trimming per quadrant (the operands carry explicit zeros there).  Measured at M = 50 (shader-clock stamps between u_small_kernel's phases): 4.4 us per
 // product for the FMA micro-tiles (bound by their LDS reads: 8 ds_read_b64 per 16 FMAs), 4.4 us for a plain MFMA loop (the LDS
 // latency of every step exposed), 2.9 us with the fragments of the next 16 k read ahead -- one wave per SIMD issues FP64 MFMAs at
 // half rate (135 cycles each here), so 512-thread blocks would halve it again.  HMOGP_SM_GEMM_FMA (compile time) restores the
@@ -194,104 +194,15 @@ __device__ __forceinline__ void sm_store(const double* __restrict__ X, double* _
   sm_each(M, [&](int i, int j) { g[(long long)i * M + j] = X[i * SLD + j]; });
 }
 
-// Lower Cholesky of X (in place, lower triangle; the strict upper triangle is left as it was), by ONE wave, left-looking, one
-// row per lane.  A wave's LDS operations are processed in order, so the lanes exchange columns through LDS without block
-// barriers.  The diagonal stays un-normalised in X until the end (no column product reads it); `diag` receives the pivots.
-// Returns LAPACK's info (0, or 1 + the first column whose pivot is <= 0 or NaN); uniform across the wave.
-__device__ __forceinline__ int sm_potrf_wave(double* X, double* diag, int M, int lane, int* progress = nullptr) {
-  int info = 0;
-  for (int j = 0; j < M; ++j) {
-    if (lane >= j && lane < M) {   // four interleaved partial sums: the loop is bound by the LDS round trip, not by the FMAs
-      const double* xi = X + lane * SLD;
-      const double* xj = X + j * SLD;
-      double s0 = xi[j], s1 = 0.0, s2 = 0.0, s3 = 0.0;
-      int k = 0;
-      for (; k + 4 <= j; k += 4) {
-        s0 = fma(-xi[k], xj[k], s0);
-        s1 = fma(-xi[k + 1], xj[k + 1], s1);
-        s2 = fma(-xi[k + 2], xj[k + 2], s2);
-        s3 = fma(-xi[k + 3], xj[k + 3], s3);
-      }
-      for (; k < j; ++k) s0 = fma(-xi[k], xj[k], s0);
-      X[lane * SLD + j] = (s0 + s1) + (s2 + s3);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const double d = X[j * SLD + j];
-    if (!(d > 0.0)) {
-      info = j + 1;
-      break;
-    }
-    const double sq = sqrt(d);
-    __builtin_amdgcn_wave_barrier();
-    if (lane == j) diag[j] = sq;
-    else if (lane > j && lane < M) X[lane * SLD + j] = X[lane * SLD + j] / sq;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // column j (hence row j of L, pivot in diag[j]) is final: a wave that follows may consume it (LDS operations of one wave are
-    // processed in order: the counter lands behind the column)
-    if (progress && lane == 0) __hip_atomic_store(progress, j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-  if (info && progress && lane == 0) __hip_atomic_store(progress, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  if (!info && lane < M) X[lane * SLD + lane] = diag[lane];
-  return info;
-}
-
-// Xi = L^-1 (L lower triangular in LDS), zeros above the diagonal: lane c owns column c (forward substitution of L x = e_c;
-// it only ever reads its own column of Xi back).  One wave; the other waves of the block may do independent work meanwhile.
-// The same, one row BEHIND a Cholesky factorisation that another wave of the block is still running: row r of L is final once the
-// factorisation has finished column r (`progress` > r; -1 = it failed); the pivots are read from `diag` (the factorisation keeps
-// the diagonal of X un-normalised until its end).  The two sequential chains overlap: ~27 + 23 us -> ~30 us at M = 50.
-__device__ __forceinline__ void sm_trtri_follow(const double* L, const double* diag, double* Xi, int M, int lane, int* progress) {
-  for (int r = 0; r < M; ++r) {
-    for (;;) {
-      const int p = __builtin_amdgcn_readfirstlane(__hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-      if (p < 0) return;
-      if (p > r) break;
-      __builtin_amdgcn_s_sleep(1);
-    }
-    asm volatile("" ::: "memory");
-    const double* lr = L + r * SLD;
-    double s0 = (lane == r) ? 1.0 : 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int k = 0;
-    for (; k + 4 <= r; k += 4) {
-      s0 = fma(-lr[k], Xi[k * SLD + lane], s0);
-      s1 = fma(-lr[k + 1], Xi[(k + 1) * SLD + lane], s1);
-      s2 = fma(-lr[k + 2], Xi[(k + 2) * SLD + lane], s2);
-      s3 = fma(-lr[k + 3], Xi[(k + 3) * SLD + lane], s3);
-    }
-    for (; k < r; ++k) s0 = fma(-lr[k], Xi[k * SLD + lane], s0);
-    const double v = (lane <= r) ? ((s0 + s1) + (s2 + s3)) / diag[r] : 0.0;
-    if (lane < SM) Xi[r * SLD + lane] = v;
-  }
-}
-
-__device__ __forceinline__ void sm_trtri_wave(const double* __restrict__ L, double* __restrict__ Xi, int M, int lane) {
-  // row by row: x[r][c] = (delta_rc - sum_{k<r} L[r][k] x[k][c]) / L[r][r]; rows above the diagonal are zeros, so every lane runs
-  // the same k-range (uniform loop, L[r][k] is an LDS broadcast, x[k][c] a conflict-free row access)
-  for (int r = 0; r < M; ++r) {
-    const double* lr = L + r * SLD;
-    double s0 = (lane == r) ? 1.0 : 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int k = 0;
-    for (; k + 4 <= r; k += 4) {
-      s0 = fma(-lr[k], Xi[k * SLD + lane], s0);
-      s1 = fma(-lr[k + 1], Xi[(k + 1) * SLD + lane], s1);
-      s2 = fma(-lr[k + 2], Xi[(k + 2) * SLD + lane], s2);
-      s3 = fma(-lr[k + 3], Xi[(k + 3) * SLD + lane], s3);
-    }
-    for (; k < r; ++k) s0 = fma(-lr[k], Xi[k * SLD + lane], s0);
-    const double v = (lane <= r) ? ((s0 + s1) + (s2 + s3)) / lr[r] : 0.0;
-    if (lane < SM) Xi[r * SLD + lane] = v;
-  }
-}
-
-// ---- the same three wave-level chains with the wave's matrix in REGISTERS --------------------------------------------------------
-// The LDS versions above pay an LDS round trip (~100+ cycles) for every dependent step: ~1100 cycles per column / row at M = 50
-// (27 us for the factorisation, 25 us for a triangular inverse).  Here lane i keeps row i of the factorised matrix (lane c:
-// column c of the inverse) in 64 registers, the loops are fully unrolled (register indices are compile-time constants), and LDS
-// only carries what crosses lanes: the finished column (one write, broadcast reads) / the finished rows of L.
+// ---- the three wave-level chains (Cholesky, triangular inverse, triangular inverse one row behind a running Cholesky), with the
+// wave's matrix in REGISTERS ----------------------------------------------------------------------------------------------------
+// A wave's LDS operations are processed in order, so the lanes of ONE wave exchange data through LDS without block barriers; the
+// other waves of the block may do independent work meanwhile.  Keeping the matrix itself in LDS would pay an LDS round trip
+// (~100+ cycles) for every dependent step: ~1100 cycles per column / row at M = 50 (27 us for the factorisation, 25 us for a
+// triangular inverse; following one row behind the factorisation overlapped the two chains: ~27 + 23 us -> ~30 us).  Here lane i
+// keeps row i of the factorised matrix (lane c: column c of the inverse) in 64 registers, the loops are fully unrolled (register
+// indices are compile-time constants), and LDS only carries what crosses lanes: the finished column (one write, broadcast reads) /
+// the finished rows of L.
 typedef __attribute__((address_space(3))) const double sm_lds_cd;   // LDS pointer that stays one (ds_read, not flat_load)
 __device__ __forceinline__ double sm_readlane(double v, int l) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
@@ -406,11 +317,6 @@ __device__ __forceinline__ void sm_trtri_regs(const double* L, const double* rdi
 // wave-level chains (Cholesky + triangular inverse of K_uu; triangular inverse of L) run on two CUs at once.  Block (q, 0) needs
 // S from block (q, 1): handed over through HBM behind an agent-scope release / acquire on flag[q] (2 Q <= 16 blocks: always
 // co-resident; S is published first thing, so the wait is never taken in practice).
-#define SM_STAMP(i)                                                                                   \
-  do {                                                                                                \
-    if (u.stamps && threadIdx.x == 0) u.stamps[((long long)blockIdx.x * 2 + blockIdx.y) * 16 + (i)] = (long long)__builtin_readcyclecounter(); \
-  } while (0)
-
 template <int P>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void u_small_kernel(SmallU u) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -427,43 +333,33 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   double* o = u.klout + (long long)q * KL_BLOCKS * 5;
 
   const int seq = (int)u.seq[0];
-  SM_STAMP(0);
   if (role == 1) {
     // ---- q(u) chain: L = flat_to_triang(L_flat) (svmogp_inf.py:193), S = L L^T (:194-195), S^-1 = dpotri(L) (:124) ------------
     for (long long e = (long long)q * NT + t; e < u.nzero; e += (long long)Q * NT) u.zero[e] = 0.0;   // (the bundle: see SmallU)
     sm_fill(X2, M, [&](int r, int c) { return (c <= r) ? u.Lflat[((long long)r * (r + 1) / 2 + c) * Q + q] : 0.0; });
     __syncthreads();
-    SM_STAMP(1);
     sm_store(X2, u.L + off, M);
     sm_gemm<false, true>(X2, X2, X0, M, 2);                // S = L L^T  -> X0
     __syncthreads();
-    SM_STAMP(2);
     sm_store(X0, u.S + off, M);
     __threadfence();                                       // S is in HBM (agent scope) ...
     __syncthreads();
     if (t == 0) __hip_atomic_store(&u.flag[q], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);   // ... before block (q, 0) may read it
-    SM_STAMP(3);
     double l2 = 0.0, ninf = 0.0;
     if (t < M) l2 = log(fabs(X2[t * SLD + t]));
     if (w == 0) {                                          // L^-1 -> X3 (one wave)
-      if (u.regs) {
-        if (lane < M) vec[5 * SM + lane] = 1.0 / X2[lane * SLD + lane];   // reciprocal pivots: one division for all rows
-        sm_wave_sync();
-        sm_trtri_regs<false>(X2, vec + 5 * SM, X3, M, lane, nullptr);
-      } else
-        sm_trtri_wave(X2, X3, M, lane);
+      if (lane < M) vec[5 * SM + lane] = 1.0 / X2[lane * SLD + lane];   // reciprocal pivots: one division for all rows
+      sm_wave_sync();
+      sm_trtri_regs<false>(X2, vec + 5 * SM, X3, M, lane, nullptr);
     }
     __syncthreads();
-    SM_STAMP(4);
     sm_gemm<true, false>(X3, X3, X1, M, 1);                // S^-1 = L^-T L^-1  -> X1
     __syncthreads();
-    SM_STAMP(5);
     sm_store(X1, u.Sqi + off, M);
     sm_each(M, [&](int i, int j) { ninf += isinf(X1[i * SLD + j]) ? 1.0 : 0.0; });
     double unused = 0.0;
     sm_block_sum3(l2, ninf, unused, red);
     if (t == 0) o[5 + 0] = 0.0, o[5 + 1] = 0.0, o[5 + 2] = 0.0, o[5 + 3] = l2, o[5 + 4] = ninf;   // KL partial "block 1"
-    SM_STAMP(6);
     return;
   }
 
@@ -491,16 +387,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   for (int e = t; e < KL_BLOCKS; e += NT)              // ... and the block maxima of diag(K_uu^-1) behind them: slot 0 below
     if (e >= 1) u.klout[(long long)Q * KL_BLOCKS * 5 + (long long)q * KL_BLOCKS + e] = 0.0;
   __syncthreads();
-  SM_STAMP(1);
-  if (u.stop_after == 1) return;
-  if (u.stop_after == 6) return;
   if (w == 0) {                                        // wave 0: L_uu = chol(K_uu + jitter I) ...
-    const int info = u.regs ? sm_potrf_regs(X0, vec, vec + 5 * SM, vec + 3 * SM, M, lane, &s_progress)
-                            : sm_potrf_wave(X0, vec, M, lane, &s_progress);
+    const int info = sm_potrf_regs(X0, vec, vec + 5 * SM, vec + 3 * SM, M, lane, &s_progress);
     if (lane == 0) s_info = info;
-  } else if (w == 1 && u.stop_after != 5) {            // ... wave 1, one row behind it: L_uu^-1 -> X1
-    if (u.regs) sm_trtri_regs<true>(X0, vec + 5 * SM, X1, M, lane, &s_progress);
-    else sm_trtri_follow(X0, vec, X1, M, lane, &s_progress);
+  } else if (w == 1) {                                 // ... wave 1, one row behind it: L_uu^-1 -> X1
+    sm_trtri_regs<true>(X0, vec + 5 * SM, X1, M, lane, &s_progress);
   } else if (w == 2) {                                 // ... wave 2 meanwhile: S of block (q, 1) (published first thing) -> X3
     if (lane == 0)
       while (__hip_atomic_load(&u.flag[q], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != seq) __builtin_amdgcn_s_sleep(2);
@@ -517,9 +408,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     }
   }
   __syncthreads();
-  SM_STAMP(2);
   if (t == 0) u.info[q] = s_info;                        // (non-zero: the engine falls back to the regular path and its ladder)
-  if (u.stop_after == 2 || u.stop_after == 5) return;
   if (s_info) return;
   // L_uu with an explicit zero upper triangle (potrf_finalize)
   sm_each(M, [&](int i, int j) { u.Luu[off + (long long)i * M + j] = (j <= i) ? X0[i * SLD + j] : 0.0; });
@@ -528,7 +417,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   __syncthreads();
   sm_gemm<true, false>(X1, X1, X0, M, 1);                // K_uu^-1 = L_uu^-T L_uu^-1            (util.py:199)            -> X0
   __syncthreads();
-  SM_STAMP(3);
   sm_store(X0, u.Kuui + off, M);
   double ma = 0.0, tr = 0.0;
   if (t < M) {                                           // a = K_uu^-1 m
@@ -537,18 +425,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     u.a[(long long)q * M + t] = sacc;
     ma = vec[SM + t] * sacc;
   }
-  SM_STAMP(4);
-  if (u.stop_after == 3) return;
   // ---- joint part: needs S of block (q, 1) -- in X3 since the factorisation (wave 2) -------------------------------------------
-  SM_STAMP(5);
   sm_each(M, [&](int i, int j) { tr += X0[i * SLD + j] * X3[i * SLD + j]; });
   sm_gemm<false, false>(X0, X3, X1, M);                  // K^-1 S                                                         -> X1
   __syncthreads();
-  SM_STAMP(6);
   sm_store(X1, u.KiS + off, M);
   sm_gemm<false, false>(X1, X0, X2, M);                  // K^-1 S K^-1                                                    -> X2
   __syncthreads();
-  SM_STAMP(7);
   sm_store(X2, u.KSK + off, M);
   sm_each(M, [&](int i, int j) {                         // C = K^-1 S K^-1 - K^-1 ; T = tril(C) + tril(C^T, -1)
     const double cij = X2[i * SLD + j] - X0[i * SLD + j];
@@ -564,7 +447,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   sm_block_sum3(tr, ma, l1, red);
   if (t == 0) o[0] = tr, o[1] = ma, o[2] = l1, o[3] = 0.0, o[4] = 0.0;
   if (t == 0) u.klout[(long long)Q * KL_BLOCKS * 5 + (long long)q * KL_BLOCKS] = kmax;
-  SM_STAMP(8);
 }
 
 // rowout[q][m] = { sum_j EK_mj, sum_j EK_mj r2_mj, sum_j (EK_mj + EK_jm)(z_j - z_m)[p] }, EK = dKmm .* K_zz: kzz_rows_kernel's
@@ -1003,39 +885,7 @@ __global__ __launch_bounds__(NT) void small_red_kernel(SmallRows a, int nblk, Sm
 
 size_t small_lds_bytes() { return sizeof(double) * (4 * SM * SLD + 6 * SM); }
 
-void launch_u_small(const SmallU& u_in, hipStream_t s) {
-  SmallU u = u_in;
-  static const int stop = [] {
-    const char* e = getenv("HMOGP_USMALL_STOP");
-    return e ? atoi(e) : 0;
-  }();
-  u.stop_after = stop;
-  static const int regs = [] {   // HMOGP_SMALL_REGS=0: the LDS-resident factorisation / inverses (A/B runs)
-    const char* e = getenv("HMOGP_SMALL_REGS");
-    return e ? atoi(e) : 1;
-  }();
-  u.regs = regs;
-  // HMOGP_USMALL_STAMPS=1: shader-clock stamps at the phase boundaries of every block, printed every 1000 launches
-  static long long* stamps = [] {
-    long long* p = nullptr;
-    const char* e = getenv("HMOGP_USMALL_STAMPS");
-    if (e && atoi(e)) (void)hipHostMalloc((void**)&p, sizeof(long long) * 8 * 2 * 16, hipHostMallocDefault);
-    return p;
-  }();
-  static int n_launch = 0;
-  if (stamps) {
-    if (++n_launch % 1000 == 0) {
-      (void)hipStreamSynchronize(s);
-      for (int q = 0; q < u.Q; ++q)
-        for (int r = 0; r < 2; ++r) {
-          const long long* t = stamps + (q * 2 + r) * 16;
-          std::fprintf(stderr, "u_small block (%d, %d): start %+lld vs (0,0);", q, r, t[0] - stamps[0]);
-          for (int i = 1; i <= (r ? 6 : 8); ++i) std::fprintf(stderr, " %d:%lld", i, t[i] - t[0]);
-          std::fprintf(stderr, "\n");
-        }
-    }
-    u.stamps = stamps;
-  }
+void launch_u_small(const SmallU& u, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {   // > 64 KB of dynamic LDS needs the opt-in
     HIP_TRY(hipFuncSetAttribute((const void*)u_small_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes()));

@@ -336,11 +336,7 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 }  // namespace
 
 bool trsm_panel_eligible(const TrsmPanelArgs& g) {
-  static const bool enabled = [] {   // HMOGP_TRSM_PANEL=0: the round-5 path (update GEMM + four substitution launches per block; A/B runs)
-    const char* e = getenv("HMOGP_TRSM_PANEL");
-    return !(e && e[0] == '0');
-  }();
-  return enabled && g.n >= 1 && g.M >= BN && (g.M % BN) == 0 && (g.ldv & 1) == 0 && (g.ldl & 1) == 0 && (g.sV & 1) == 0 &&
+  return g.n >= 1 && g.M >= BN && (g.M % BN) == 0 && (g.ldv & 1) == 0 && (g.ldl & 1) == 0 && (g.sV & 1) == 0 &&
          (g.sL & 1) == 0 && al16(g.V) && al16(g.Lsym) && (!g.Vsrc || al16(g.Vsrc)) && g.rdiag != nullptr;
 }
 

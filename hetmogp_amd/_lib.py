@@ -22,6 +22,7 @@ LIK_NEGBINOMIAL = 11     # heteroscedastic Negative Binomial for over-dispersed 
 LIK_WEIBULL = 12         # Weibull with right-censoring (not in the reference); no lik_param, Y is (N, 2) = (time, event indicator)
 LIK_IDS_BY_NAME = dict(Gaussian=0, Bernoulli=1, HetGaussian=2, Categorical=3, Poisson=4, Exponential=5, Gamma=6, Beta=7,
                        Student=8, Ordinal=9, Dirichlet=10, NegBinomial=11, Weibull=12)
+QUANT_MAXP = 8          # most probabilities per hmogp_predictive_quantile / hmogp_predict_quantile call
 E_INVALID, E_NO_DEVICE, E_NOT_PD, E_SQI_UNSTABLE, E_STATE, E_COMM = -1, -2, -3, -4, -5, -6
 NTIMINGS = 11
 COMM_ID_BYTES = 128
@@ -137,6 +138,12 @@ EXPORTS = {
                                           c_double_p, c_double_p, c_double_p]),
     "hmogp_predict_log_density": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_int64, C.c_int32, c_double_p,
                                             c_double_p]),
+    "hmogp_predictive_cdf": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                       c_double_p, c_double_p]),
+    "hmogp_predictive_quantile": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, C.c_int32, c_double_p, c_double_p,
+                                            c_double_p, c_double_p]),
+    "hmogp_predict_cdf": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_int64, C.c_int32, c_double_p, c_double_p]),
+    "hmogp_predict_quantile": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, C.c_int32, c_double_p, C.c_int32, c_double_p]),
     "hmogp_sample": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint64, c_double_p, c_double_p]),
     "hmogp_bench_contraction": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, c_double_p]),
     "hmogp_host_alloc": (C.c_void_p, [C.c_uint64]),

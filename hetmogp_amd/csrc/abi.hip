@@ -76,6 +76,22 @@ void upload_y_image(int lik_id, double lik_param, const OrdinalTable* tb, const 
   dy.ensure(sizeof(double) * 2 * N);
   HIP_TRY(hipMemcpy(dy.p, cuts.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
 }
+void upload_y_cdf(int lik_id, double lik_param, const OrdinalTable* tb, const double* y, long long N, DevBuf& dy) {
+  if (lik_id != HMOGP_LIK_WEIBULL) {
+    upload_y_image(lik_id, lik_param, tb, y, N, dy);
+    return;
+  }
+  std::vector<double> ly((size_t)N);
+  for (long long n = 0; n < N; ++n) ly[n] = y[n] > 0.0 ? std::log(y[n]) : (y[n] <= 0.0 ? -INFINITY : y[n]);
+  dy.ensure(sizeof(double) * N);
+  HIP_TRY(hipMemcpy(dy.p, ly.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+}
+
+int predq_nodes(int lik_id, int gh_T) {
+  if (const char* why = predq_refusal(lik_id)) throw EngineError{HMOGP_E_INVALID, why};
+  if (gh_T != 0 && gh_T != 10 && gh_T != 20) throw EngineError{HMOGP_E_INVALID, "gh_T must be 0, 10 or 20"};
+  return gh_T == 0 ? 20 : gh_T;
+}
 }  // namespace hmogp_detail
 
 extern "C" {
@@ -608,6 +624,82 @@ int hmogp_predict_log_density(hmogp_handle h, int32_t t, const double* Xnew, con
     if (!h->evaluated && !h->began) throw EngineError{HMOGP_E_STATE, "no evaluation to predict from"};
     if (t < 0 || t >= h->T) throw EngineError{HMOGP_E_INVALID, "task index out of range"};
     h->predict_log_density(t, Xnew, Ynew, Nnew, lpd_nodes(h->tasks[t].lik, gh_T), lpd, ess);
+  });
+}
+
+// the building blocks of the predictive cdf / survival function / quantiles; q != nullptr: quantiles
+static void predq_rows(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, const double* y, const double* m,
+                       const double* v, double* cdf, double* sf, int32_t nP, const double* p, double* q) {
+  PqArgs a;
+  a.T = predq_nodes(lik_id, gh_T);
+  if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
+  const int J = lik_dimf(lik_id, lik_param);
+  check_lik_param(lik_id, lik_param);
+  const bool quant = q != nullptr || nP != 0;
+  if (quant && (nP < 1 || nP > HMOGP_QUANT_MAXP)) throw EngineError{HMOGP_E_INVALID, "nP must be in 1 .. HMOGP_QUANT_MAXP"};
+  if (N < 0 || (N > 0 && (!m || !v || (quant ? (!p || !q) : !y)))) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
+  if (N == 0) return;
+  need_device(device);
+  DevBuf dy, dm, dv, d1, d2;
+  const OrdinalTable* tb = lik_id == HMOGP_LIK_ORDINAL ? &ordinal_table(lik_param) : nullptr;
+  if (!quant) upload_y_cdf(lik_id, lik_param, nullptr, y, N, dy);
+  dm.ensure(sizeof(double) * N * J), dv.ensure(sizeof(double) * N * J);
+  HIP_TRY(hipMemcpy(dm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
+  a.lik = lik_id, a.N = N, a.param = tb ? tb->sigma : lik_param, a.table = tb;
+  a.m = dm.d(), a.v = dv.d(), a.ldf = J;
+  if (quant) {
+    d1.ensure(sizeof(double) * N * nP);
+    a.nP = nP, a.q = d1.d();
+    for (int i = 0; i < nP; ++i) a.p[i] = p[i];
+    launch_predictive_quantile(a, nullptr);
+  } else {
+    if (cdf) d1.ensure(sizeof(double) * N);
+    if (sf) d2.ensure(sizeof(double) * N);
+    a.y = dy.d(), a.ldy = N, a.cdf = cdf ? d1.d() : nullptr, a.sf = sf ? d2.d() : nullptr;
+    launch_predictive_cdf(a, nullptr);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  if (quant) HIP_TRY(hipMemcpy(q, d1.p, sizeof(double) * N * nP, hipMemcpyDeviceToHost));
+  if (!quant && cdf) HIP_TRY(hipMemcpy(cdf, d1.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+  if (!quant && sf) HIP_TRY(hipMemcpy(sf, d2.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+}
+
+int hmogp_predictive_cdf(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, const double* y, const double* m,
+                         const double* v, double* cdf, double* sf) {
+  return guarded(nullptr, [&] { predq_rows(device, lik_id, lik_param, gh_T, N, y, m, v, cdf, sf, 0, nullptr, nullptr); });
+}
+
+int hmogp_predictive_quantile(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, int32_t nP, const double* p,
+                              const double* m, const double* v, double* q) {
+  return guarded(nullptr, [&] {
+    if (nP < 1 || nP > HMOGP_QUANT_MAXP) throw EngineError{HMOGP_E_INVALID, "nP must be in 1 .. HMOGP_QUANT_MAXP"};
+    if (N > 0 && !q) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
+    predq_rows(device, lik_id, lik_param, gh_T, N, nullptr, m, v, nullptr, nullptr, nP, p, q);
+  });
+}
+
+int hmogp_predict_cdf(hmogp_handle h, int32_t t, const double* Xnew, const double* ynew, int64_t Nnew, int32_t gh_T, double* cdf,
+                      double* sf) {
+  if (!h) return HMOGP_E_INVALID;
+  return guarded(h, [&] {
+    if (!h->evaluated && !h->began) throw EngineError{HMOGP_E_STATE, "no evaluation to predict from"};
+    if (t < 0 || t >= h->T) throw EngineError{HMOGP_E_INVALID, "task index out of range"};
+    if (Nnew > 0 && !ynew) throw EngineError{HMOGP_E_INVALID, "bad predict arguments"};
+    h->predict_cdf_quantile(t, Xnew, ynew, Nnew, predq_nodes(h->tasks[t].lik, gh_T), cdf, sf, 0, nullptr, nullptr);
+  });
+}
+
+int hmogp_predict_quantile(hmogp_handle h, int32_t t, const double* Xnew, int64_t Nnew, int32_t nP, const double* p, int32_t gh_T,
+                           double* q) {
+  if (!h) return HMOGP_E_INVALID;
+  return guarded(h, [&] {
+    if (!h->evaluated && !h->began) throw EngineError{HMOGP_E_STATE, "no evaluation to predict from"};
+    if (t < 0 || t >= h->T) throw EngineError{HMOGP_E_INVALID, "task index out of range"};
+    if (nP < 1 || nP > HMOGP_QUANT_MAXP) throw EngineError{HMOGP_E_INVALID, "nP must be in 1 .. HMOGP_QUANT_MAXP"};
+    if (Nnew > 0 && (!p || !q)) throw EngineError{HMOGP_E_INVALID, "bad predict arguments"};
+    h->predict_cdf_quantile(t, Xnew, nullptr, Nnew, predq_nodes(h->tasks[t].lik, gh_T), nullptr, nullptr, nP, p, q);
   });
 }
 

@@ -151,6 +151,11 @@ double ordinal_register(int K, const double* edges, double sigma);
 // y of a building block (or new rows of a task) -> device, checked, in the image the row kernels read (abi.hip): [N]; Ordinal [2][N] cut points
 // by `tb`, or by the registry entry `lik_param` names when tb is null; Dirichlet [K][N] log y_k; Weibull [2][N] (log y, delta)
 void upload_y_image(int lik_id, double lik_param, const OrdinalTable* tb, const double* y, long long N, DevBuf& dy);
+// y [N] of the predictive cdf -> device, in the image predq.hip reads: Weibull log y (-inf for y <= 0: the row is (0, 1)); Ordinal
+// the [2][N] cut points of upload_y_image (labels checked); every other family as it is
+void upload_y_cdf(int lik_id, double lik_param, const OrdinalTable* tb, const double* y, long long N, DevBuf& dy);
+// nodes per dimension of the cdf / quantile kernels: 0 = 20; HMOGP_E_INVALID for a family predq.hip refuses (with its reason) or another gh_T
+int predq_nodes(int lik_id, int gh_T);
 
 // Row ranges per weighted-Gram launch: a multiple of 8 (one range per XCD at a time), each >= 32 k-steps of 16 rows,
 // enough blocks (lower tiles x ranges) for >= 8 rounds over the 256 CUs, at most KS_MAX slabs.
@@ -539,6 +544,9 @@ struct hmogp_engine {
   void qf_chunk(const double* Xchunk, long long n, DevBuf& dX, DevBuf& dm, DevBuf& dv);
   // deterministic log predictive density of task t's rows: q(f) stays on the device, only lpd / ess come back; T = nodes per dimension
   void predict_log_density(int t, const double* Xnew, const double* Ynew, long long Nnew, int T, double* lpd, double* ess);
+  // q != nullptr: quantiles of the nP probabilities p, else cdf / sf (either may be null) of ynew
+  void predict_cdf_quantile(int t, const double* Xnew, const double* ynew, long long Nnew, int T, double* cdf, double* sf, int nP,
+                            const double* p, double* q);
 
   // ---- likelihood parameters (lik_param.hip) ----
   bool lik_grad_on = false;      // hmogp_lik_grad_enable: persistent

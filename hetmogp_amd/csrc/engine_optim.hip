@@ -277,3 +277,49 @@ void hmogp_engine::predict_log_density(int t, const double* Xnew, const double* 
   HIP_TRY(hipMemcpy(lpd, dl.p, sizeof(double) * Nnew, hipMemcpyDeviceToHost));
   if (ess) HIP_TRY(hipMemcpy(ess, de.p, sizeof(double) * Nnew, hipMemcpyDeviceToHost));
 }
+
+// predict_log_density's loop with the cdf / quantile kernels behind q(f).  Every check comes before the first launch.
+void hmogp_engine::predict_cdf_quantile(int t, const double* Xnew, const double* ynew, long long Nnew, int T_, double* cdf, double* sf,
+                                        int nP, const double* p, double* q) {
+  if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to predict from"};
+  if (t < 0 || t >= T) throw EngineError{HMOGP_E_INVALID, "task index out of range"};
+  const Task& k = tasks[t];
+  if (const char* why = predq_refusal(k.lik)) throw EngineError{HMOGP_E_INVALID, why};
+  const bool quant = q != nullptr;
+  if (quant && (nP < 1 || nP > HMOGP_QUANT_MAXP || !p)) throw EngineError{HMOGP_E_INVALID, "nP must be in 1 .. HMOGP_QUANT_MAXP"};
+  if (Nnew < 0 || (Nnew > 0 && (!Xnew || (!quant && !ynew)))) throw EngineError{HMOGP_E_INVALID, "bad predict arguments"};
+  if (Nnew == 0) return;
+  HIP_TRY(hipSetDevice(device));
+  DevBuf dy, d1, d2;
+  const OrdinalTable* tb = k.lik == HMOGP_LIK_ORDINAL ? &task_table(k) : nullptr;
+  if (!quant) upload_y_cdf(k.lik, k.param, tb, ynew, Nnew, dy);   // (checks the labels; throws before anything is launched)
+  if (quant) d1.ensure(sizeof(double) * Nnew * nP);
+  if (!quant && cdf) d1.ensure(sizeof(double) * Nnew);
+  if (!quant && sf) d2.ensure(sizeof(double) * Nnew);
+  ensure_workspace(std::min(chunk, std::max<long long>(Nnew, 1)));
+  ensure_strict_workspace();
+  const long long ldn = ws_rows;
+  DevBuf dX, dm, dv;
+  dX.ensure(sizeof(double) * ldn * P), dm.ensure(sizeof(double) * ldn * Df), dv.ensure(sizeof(double) * ldn * Df);
+  for (long long r0 = 0; r0 < Nnew; r0 += ldn) {
+    const long long n = std::min(ldn, Nnew - r0);
+    qf_chunk(Xnew + r0 * P, n, dX, dm, dv);
+    PqArgs a;
+    a.lik = k.lik, a.T = T_, a.param = k.qparam, a.table = tb, a.N = n;
+    a.m = dm.d() + k.d0, a.v = dv.d() + k.d0, a.ldf = Df, a.absv = true;
+    if (quant) {
+      a.nP = nP, a.q = d1.d() + r0 * nP;
+      for (int i = 0; i < nP; ++i) a.p[i] = p[i];
+      launch_predictive_quantile(a, st);
+    } else {
+      a.y = dy.d() + r0, a.ldy = Nnew;
+      a.cdf = cdf ? d1.d() + r0 : nullptr, a.sf = sf ? d2.d() + r0 : nullptr;
+      launch_predictive_cdf(a, st);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (dX is reused by the next chunk's upload)
+  }
+  if (quant) HIP_TRY(hipMemcpy(q, d1.p, sizeof(double) * Nnew * nP, hipMemcpyDeviceToHost));
+  if (!quant && cdf) HIP_TRY(hipMemcpy(cdf, d1.p, sizeof(double) * Nnew, hipMemcpyDeviceToHost));
+  if (!quant && sf) HIP_TRY(hipMemcpy(sf, d2.p, sizeof(double) * Nnew, hipMemcpyDeviceToHost));
+}

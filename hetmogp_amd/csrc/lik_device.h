@@ -1480,3 +1480,49 @@ __device__ __forceinline__ double lik_beta_logpdf(double y, const double* f) {
   const double a = clip(safe_exp(f[0]), 1e-9, 1e9), b = clip(safe_exp(f[1]), 1e-9, 1e9);
   return (a - 1.0) * log(y) + (b - 1.0) * log(1.0 - y) - (lgamma(a) + lgamma(b) - lgamma(a + b));
 }
+
+// ============================================================================ predictive cdf / survival function
+// The conditional pair C = P(Y <= y | f), S = P(Y > y | f) at one node of the rule, for the six families whose pair is closed-form in exp,
+// expm1, log and erfc.  Each is evaluated directly, never as 1 - the other: a tail of 1e-200 keeps its relative precision.  Links and clips
+// are those of lik_logpdf_sample<LIK> / lik_weibull_logpdf.  What the arguments mean per family:
+//   Gaussian      z = (y - f0) / param                           param: the standard deviation (sqrt(sigma^2 + v) folds q(f) in exactly)
+//   HetGaussian   z = (y - f0) / sqrt(yaux + safe_exp(f1))       yaux: the variance of f0 integrated out analytically (0: the plain conditional)
+//   Ordinal       z = (yaux - f0) / param                        yaux: the label's UPPER cut point (+inf for class K), param as Gaussian's
+//                 C = erfc(-z / sqrt 2) / 2,  S = erfc(z / sqrt 2) / 2
+//   Bernoulli     p = clip(e^f / (1 + e^f), 1e-9, 1 - 1e-9):  (0, 1) for y < 0, (1 - p, p) for 0 <= y < 1, (1, 0) for y >= 1
+//   Exponential   b = clip(safe_exp(-f0), 1e-9, 1e9):  (0, 1) for y <= 0, else S = exp(-y / b), C = -expm1(-y / b)
+//   Weibull       y is log(time) (-inf: time <= 0 -> (0, 1)), k = weibull_shape(f1), z = min(k (y - f0), HMOGP_WEIBULL_ZMAX), e = exp(z),
+//                 S = exp(-e), C = -expm1(-e)
+// Appended, like the sections above, so that nothing in front changes.
+__device__ __forceinline__ void phi_cdf_sf(double z, double& C, double& S) {
+  C = 0.5 * erfc(-z * M_SQRT1_2);
+  S = 0.5 * erfc(z * M_SQRT1_2);
+}
+template <int LIK>
+__device__ __forceinline__ void lik_cdf_sf(double y, double yaux, const double* f, double param, double& C, double& S) {
+  if (LIK == HMOGP_LIK_GAUSSIAN) {
+    phi_cdf_sf((y - f[0]) / param, C, S);
+  } else if (LIK == HMOGP_LIK_HETGAUSSIAN) {
+    phi_cdf_sf((y - f[0]) / sqrt(yaux + safe_exp(f[1])), C, S);
+  } else if (LIK == HMOGP_LIK_ORDINAL) {
+    phi_cdf_sf((yaux - f[0]) / param, C, S);
+  } else if (LIK == HMOGP_LIK_BERNOULLI) {
+    const double ef = safe_exp(f[0]);
+    const double p = clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9);
+    C = y < 0.0 ? 0.0 : (y < 1.0 ? 1.0 - p : 1.0);
+    S = y < 0.0 ? 1.0 : (y < 1.0 ? p : 0.0);
+    if (y != y) C = S = y;
+  } else if (LIK == HMOGP_LIK_EXPONENTIAL) {
+    const double b = clip(safe_exp(-f[0]), 1e-9, 1e9);
+    const double a = -(y / b);
+    C = y <= 0.0 ? 0.0 : -expm1(a);
+    S = y <= 0.0 ? 1.0 : exp(a);
+  } else if (LIK == HMOGP_LIK_WEIBULL) {
+    const double k = weibull_shape(f[1]);
+    const double e = exp(fmin(k * (y - f[0]), HMOGP_WEIBULL_ZMAX));
+    C = y == -INFINITY ? 0.0 : -expm1(-e);
+    S = y == -INFINITY ? 1.0 : exp(-e);
+  } else {
+    C = S = nan("");
+  }
+}

@@ -193,6 +193,29 @@ struct LpdArgs {
   double *lpd = nullptr, *ess = nullptr;
 };
 void launch_log_predictive_gh(const LpdArgs& a, hipStream_t s);
+// Predictive cdf / survival function / quantiles per row (predq.hip) over the same nodes and weights, for Gaussian,
+// HetGaussian, Bernoulli, Exponential, Ordinal and Weibull; m, v, ldf, absv as in LpdArgs.  `y` (cdf only): [N]; Ordinal [2][ldy] cut
+// points (the upper one is read); Weibull [N] log of the time, -inf for a time <= 0.  `param`: sigma (Gaussian, Ordinal -- not the
+// table id).  `table`: the Ordinal table (quantiles only).  cdf / sf: [N], either may be null.  q: [N][nP], p: nP <= HMOGP_QUANT_MAXP
+// probabilities (one outside (0, 1): NaN in its column).  T: 10 or 20.
+struct PqArgs {
+  int lik = 0, T = 20;
+  double param = 0.0;
+  const OrdinalTable* table = nullptr;
+  long long N = 0;
+  const double* y = nullptr;
+  long long ldy = 0;
+  const double *m = nullptr, *v = nullptr;
+  int ldf = 1;
+  bool absv = false;
+  double *cdf = nullptr, *sf = nullptr;
+  int nP = 0;
+  double p[HMOGP_QUANT_MAXP] = {};
+  double* q = nullptr;
+};
+const char* predq_refusal(int lik);   // nullptr for the six families, else the reason the family is refused
+void launch_predictive_cdf(const PqArgs& a, hipStream_t s);
+void launch_predictive_quantile(const PqArgs& a, hipStream_t s);
 // Y[n] ~ p(y | F[n]): the reference's `<likelihood>.samples`, one draw per row, counter-based generator
 void launch_sample(int lik, int J, double param, long long N, unsigned long long seed, const double* F, double* Y,
                    hipStream_t s);

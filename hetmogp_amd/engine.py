@@ -461,6 +461,32 @@ class Engine(object):
         check(lib.hmogp_predict_log_density(self._h, int(t), _p(Xnew), _p(Ynew), n, int(gh_T), _p(lpd), _p(ess)), self._h)
         return lpd, ess
 
+    def predict_cdf(self, t, Xnew, ynew, gh_T=0):
+        """(cdf, sf) of task t's new rows (hmogp_predict_cdf): q(f) at Xnew stays on the device and feeds the cdf kernels with
+        the task's CURRENT likelihood parameters.  ynew: (N,) values (Ordinal: labels; Weibull: times, no indicator column)."""
+        Xnew = _f64(Xnew).reshape(-1, self.P)
+        ynew = _f64(ynew).reshape(-1)
+        n = Xnew.shape[0]
+        if ynew.shape[0] != n:
+            raise _lib.InvalidArgument("predict_cdf: Xnew has %d rows, ynew %d" % (n, ynew.shape[0]))
+        cdf, sf = np.zeros(n), np.zeros(n)
+        check(lib.hmogp_predict_cdf(self._h, int(t), _p(Xnew), _p(ynew), n, int(gh_T), _p(cdf), _p(sf)), self._h)
+        return cdf, sf
+
+    def predict_quantile(self, t, Xnew, probs, gh_T=0):
+        """(N, len(probs)) quantiles of task t's new rows (hmogp_predict_quantile); probs in (0, 1), any number of them
+        (the library takes _lib.QUANT_MAXP per call)."""
+        Xnew = _f64(Xnew).reshape(-1, self.P)
+        probs = _f64(probs).reshape(-1)
+        n = Xnew.shape[0]
+        out = np.zeros((n, probs.shape[0]))
+        for c0 in range(0, max(probs.shape[0], 1), _lib.QUANT_MAXP):
+            pc = np.ascontiguousarray(probs[c0:c0 + _lib.QUANT_MAXP])
+            qc = np.zeros((n, pc.shape[0]))
+            check(lib.hmogp_predict_quantile(self._h, int(t), _p(Xnew), n, pc.shape[0], _p(pc), int(gh_T), _p(qc)), self._h)
+            out[:, c0:c0 + pc.shape[0]] = qc
+        return out
+
     def graph_stats(self):
         """(graphs captured, evaluations replayed) of the small-model hipGraph mechanism (hmogp_graph_stats)."""
         cap, rep = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
@@ -626,6 +652,51 @@ def log_predictive_density_rows(name, y, m, v, gh_T=0, return_ess=False, device=
     check(lib.hmogp_log_predictive_gh(device, LIK_IDS[name], lik_param(name, **kw), int(gh_T), y.shape[0], _p(y), _p(m), _p(v),
                                       _p(lpd), _p(ess) if return_ess else None))
     return (lpd, ess) if return_ess else lpd
+
+
+PREDQ_FAMILIES = ("Gaussian", "HetGaussian", "Bernoulli", "Exponential", "Ordinal", "Weibull")
+PREDQ_MISSING = {"Poisson": "a regularised incomplete gamma function", "Gamma": "a regularised incomplete gamma function",
+                 "Beta": "a regularised incomplete beta function", "Student": "a regularised incomplete beta function",
+                 "NegBinomial": "a regularised incomplete beta function", "Categorical": "an order of its classes (it has none)",
+                 "Dirichlet": "a univariate outcome (it is multivariate)"}
+
+
+def predq_require(name):
+    """NotImplementedError naming the family and what its predictive cdf would need (six families are built)."""
+    if name not in PREDQ_FAMILIES:
+        raise NotImplementedError("predictive cdf / quantiles of %s need %s, which is not built" % (name, PREDQ_MISSING.get(name, "?")))
+
+
+def predictive_cdf_rows(name, y, m, v, gh_T=0, return_sf=False, device=None, **kw):
+    """Per-row predictive cdf P(Y <= y_n) under q(f) = N(m_n, diag v_n) over the nodes of `log_predictive_density_rows` (DESIGN 9k);
+    return_sf=True: (cdf, sf), the survival function P(Y > y_n) summed on its own (a tail of 1e-200 keeps its digits).  y: (N,) --
+    Ordinal labels, Weibull times.  Gaussian, HetGaussian, Bernoulli, Exponential, Ordinal, Weibull; the others InvalidArgument."""
+    device = _resolve_device(device)
+    y, m, v = _f64(y).reshape(-1), _f64(m), _f64(v)
+    J = lik_dim_f(name, **kw)
+    m, v = m.reshape(-1, J), v.reshape(-1, J)
+    cdf = np.zeros(y.shape[0])
+    sf = np.zeros(y.shape[0]) if return_sf else None
+    check(lib.hmogp_predictive_cdf(device, LIK_IDS[name], lik_param(name, **kw), int(gh_T), y.shape[0], _p(y), _p(m), _p(v), _p(cdf),
+                                   _p(sf) if return_sf else None))
+    return (cdf, sf) if return_sf else cdf
+
+
+def predictive_quantile_rows(name, m, v, probs, gh_T=0, device=None, **kw):
+    """(N, len(probs)) predictive quantiles under q(f) = N(m_n, diag v_n): the y with cdf(y) = p; Bernoulli / Ordinal the
+    smallest point of the support whose cdf is >= p.  A p outside (0, 1) gives a NaN column."""
+    device = _resolve_device(device)
+    m, v, probs = _f64(m), _f64(v), _f64(probs).reshape(-1)
+    J = lik_dim_f(name, **kw)
+    m, v = m.reshape(-1, J), v.reshape(-1, J)
+    out = np.zeros((m.shape[0], probs.shape[0]))
+    for c0 in range(0, max(probs.shape[0], 1), _lib.QUANT_MAXP):
+        pc = np.ascontiguousarray(probs[c0:c0 + _lib.QUANT_MAXP])
+        qc = np.zeros((m.shape[0], pc.shape[0]))
+        check(lib.hmogp_predictive_quantile(device, LIK_IDS[name], lik_param(name, **kw), int(gh_T), m.shape[0], pc.shape[0], _p(pc),
+                                            _p(m), _p(v), _p(qc)))
+        out[:, c0:c0 + pc.shape[0]] = qc
+    return out
 
 
 def sample(name, F, seed=0, device=None, **kw):

@@ -90,6 +90,19 @@ class _Lik(object):
         warn_low_ess([ess], [(self.name, self.kwargs())])
         return (lpd, ess) if return_ess else lpd
 
+    def predictive_cdf(self, Ytest, m, v, gh_T=0, return_sf=False):
+        """Per-row predictive cdf P(Y <= y) (N,) of DESIGN 9k; return_sf=True: (cdf, sf).  Ytest: (N,) values (Ordinal labels, Weibull
+        times).  NotImplementedError for a family whose cdf needs a special function that is not built."""
+        from .engine import predictive_cdf_rows, predq_require
+        predq_require(self.name)
+        return predictive_cdf_rows(self.name, Ytest, m, v, gh_T=gh_T, return_sf=return_sf, **self.kwargs())
+
+    def predictive_quantiles(self, m, v, probs, gh_T=0):
+        """(N, len(probs)) predictive quantiles of DESIGN 9k; probs are probabilities in (0, 1)."""
+        from .engine import predictive_quantile_rows, predq_require
+        predq_require(self.name)
+        return predictive_quantile_rows(self.name, m, v, probs, gh_T=gh_T, **self.kwargs())
+
     def predictive(self, m, v, gh_points=None, Y_metadata=None):
         """Predictive mean / variance of y (the reference's `predictive`; Gauss-Hermite order of a fresh instance)."""
         from .engine import predictive
@@ -428,6 +441,23 @@ class HetLikelihood(object):
                for t, l in enumerate(self.likelihoods_list)]
         warn_low_ess([o[1] for o in out], self.specs())
         return [o[0] for o in out]
+
+    def _predq_tasks(self, tasks):
+        from .engine import predq_require
+        tasks = list(range(len(self.likelihoods_list))) if tasks is None else [int(t) for t in tasks]
+        for t in tasks:                                      # (every refusal before the first launch)
+            predq_require(self.likelihoods_list[t].name)
+        return tasks
+
+    def predictive_cdf(self, Ytest, mu_F, v_F, Y_metadata=None, return_sf=False, tasks=None, gh_T=0):
+        """One (N_t,) cdf -- or (cdf, sf) pair -- per requested task (DESIGN 9k); the lists are indexed by task.  tasks=None: all tasks;
+        NotImplementedError when one of them has no predictive cdf."""
+        return [self.likelihoods_list[t].predictive_cdf(Ytest[t], mu_F[t], v_F[t], gh_T=gh_T, return_sf=return_sf)
+                for t in self._predq_tasks(tasks)]
+
+    def predictive_quantiles(self, mu_F, v_F, probs, Y_metadata=None, tasks=None, gh_T=0):
+        """One (N_t, len(probs)) array of quantiles per requested task; probs are probabilities in (0, 1)."""
+        return [self.likelihoods_list[t].predictive_quantiles(mu_F[t], v_F[t], probs, gh_T=gh_T) for t in self._predq_tasks(tasks)]
 
     def var_exp_derivatives(self, Y, mu_F, v_F, Y_metadata):
         out = [l.var_exp_derivatives(Y[t], mu_F[t], v_F[t]) for t, l in enumerate(self.likelihoods_list)]

@@ -950,6 +950,61 @@ class SVMOGP(object):
         warn_low_ess(ess, self.likelihood.specs())
         return (lpd, ess) if return_ess else lpd
 
+    def _predq_tasks(self, tasks, route):
+        if route not in ("default", "reference"):
+            raise ValueError("route must be 'default' or 'reference'")
+        return self.likelihood._predq_tasks(tasks)           # (NotImplementedError before anything is launched)
+
+    def predict_quantiles(self, Xpred, quantiles=(2.5, 97.5), tasks=None, route="default", gh_T=0):
+        """Predictive quantiles of the outputs at Xpred[t] (GPy's `predict_quantiles`): `quantiles` are PERCENTAGES, the
+        result one (N_t, len(quantiles)) array per requested task, in the order of `tasks` (None: all tasks).  Built for Gaussian,
+        HetGaussian, Bernoulli, Exponential, Ordinal and Weibull; any other family among the requested tasks raises NotImplementedError
+        naming it and the special function its cdf needs.  route="default": q(f) on the device, the engine's current likelihood
+        parameters (`hmogp_predict_quantile`); route="reference": q(f) from `_raw_predict_f`, then the stand-alone building block."""
+        from .engine import predictive_quantile_rows
+        probs = np.asarray(quantiles, dtype=float).reshape(-1) / 100.0
+        out = []
+        for t in self._predq_tasks(tasks, route):
+            l = self.likelihood.likelihoods_list[t]
+            if route == "default":
+                self._refresh()
+                out.append(self._engine.predict_quantile(t, np.asarray(Xpred[t], dtype=float).reshape(-1, self.Xdim), probs, gh_T=gh_T))
+            else:
+                m, v = self._predict_route(Xpred[t], t, route)
+                out.append(predictive_quantile_rows(l.name, m, v, probs, gh_T=gh_T, device=self._engine_device(), **l.kwargs()))
+        return out
+
+    def predictive_cdf(self, Xtest, Ytest, return_sf=False, tasks=None, route="default", gh_T=0):
+        """Predictive cdf P(Y <= y) of the rows (Xtest[t], Ytest[t]): one (N_t,) array per requested task, or a (cdf, sf)
+        pair with return_sf=True -- sf = P(Y > y) summed on its own, never 1 - cdf.  Xtest / Ytest are indexed by task; Ytest[t] is
+        (N_t,): values, Ordinal labels, Weibull times.  Families, tasks and routes as in `predict_quantiles`."""
+        from .engine import predictive_cdf_rows
+        out = []
+        for t in self._predq_tasks(tasks, route):
+            l = self.likelihood.likelihoods_list[t]
+            if route == "default":
+                self._refresh()
+                c, s_ = self._engine.predict_cdf(t, np.asarray(Xtest[t], dtype=float).reshape(-1, self.Xdim), Ytest[t], gh_T=gh_T)
+            else:
+                m, v = self._predict_route(Xtest[t], t, route)
+                c, s_ = predictive_cdf_rows(l.name, Ytest[t], m, v, gh_T=gh_T, return_sf=True, device=self._engine_device(), **l.kwargs())
+            out.append((c, s_) if return_sf else c)
+        return out
+
+    def survival_function(self, t, X, times, gh_T=0):
+        """Survival curves S(time | x) of the Weibull task t: (N, len(times)), row n the probability that the event at
+        X[n] is later than each of `times`.  q(f) is formed once with `predict_f`; the building block then runs on the tiled rows."""
+        from .engine import predictive_cdf_rows
+        l = self.likelihood.likelihoods_list[int(t)]
+        if l.name != "Weibull":
+            raise ValueError("survival_function: task %d is %s, not Weibull" % (int(t), l.name))
+        times = np.asarray(times, dtype=float).reshape(-1)
+        m, v = self._predict_route(np.asarray(X, dtype=float).reshape(-1, self.Xdim), int(t), "default")
+        n, k = m.shape[0], times.shape[0]
+        _, sf = predictive_cdf_rows("Weibull", np.tile(times, n), np.repeat(m, k, axis=0), np.repeat(v, k, axis=0), gh_T=gh_T,
+                                    return_sf=True, device=self._engine_device())
+        return sf.reshape(n, k)
+
     def negative_log_predictive(self, Xtest, Ytest, num_samples=1000, seed=0, route="default", method="mc"):
         """svmogp.py:353-370.  q(f) at the test inputs: route="default" from `predict_f`, route="reference" through
         `_raw_predict_f` as the reference does (see `predictive`).  method="mc" (default): the reference's Monte-Carlo estimate with

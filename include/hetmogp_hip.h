@@ -482,6 +482,40 @@ int hmogp_log_predictive_gh(int32_t device, int32_t lik_id, double lik_param, in
 int hmogp_predict_log_density(hmogp_handle h, int32_t t, const double* Xnew, const double* Ynew, int64_t Nnew, int32_t gh_T,
                               double* lpd /* [Nnew] */, double* ess /* [Nnew] or NULL */);
 
+/* Predictive cdf, survival function and quantiles per test row, over the nodes and normalised weights of
+ * hmogp_log_predictive_gh: cdf[n] = sum_nodes w C(y_n | f_node), sf[n] = sum_nodes w S(y_n | f_node) with the family's conditional cdf C
+ * and survival function S, each evaluated directly (never as 1 - the other: a tail of 1e-200 keeps its relative precision), links and
+ * clips as in hmogp_log_predictive.  Built for the six families whose pair is closed-form in exp, expm1, log and erfc:
+ *   Gaussian     closed form, z = (y - m) / sqrt(sigma^2 + v) (lik_param <= 0: sigma = 0.5): cdf = erfc(-z / sqrt 2) / 2, sf = erfc(z / sqrt 2) / 2
+ *   HetGaussian  f0 integrated analytically, gh_T nodes over f1: z_j = (y - m0) / sqrt(v0 + safe_exp(f1_j))
+ *   Bernoulli    p1 = sum w clip(e^f / (1 + e^f), 1e-9, 1 - 1e-9), p0 = sum w (1 - that): (0, 1) for y < 0, (p0, p1) for 0 <= y < 1, (1, 0) for y >= 1
+ *   Exponential  b = clip(safe_exp(-f), 1e-9, 1e9): (0, 1) for y <= 0, else S = exp(-y / b), C = -expm1(-y / b)
+ *   Ordinal      closed form; y is the label c in 1 .. K (anything else: HMOGP_E_INVALID): P(Y <= c) = Phi((b_c - m) / sqrt(sigma^2 + v)), b_K = +inf
+ *   Weibull      y is a TIME, [N] with no indicator column: (0, 1) for y <= 0, else k = shape(f1), z = min(k (log y - f0), 680), e = exp(z),
+ *                S = exp(-e), C = -expm1(-e); the gh_T x gh_T tensor rule
+ * Every other family is HMOGP_E_INVALID with the reason in the error string: Poisson and Gamma need a regularised incomplete gamma
+ * function, Beta, Student and NegBinomial a regularised incomplete beta function, Categorical has no order, Dirichlet is multivariate.
+ * gh_T: 0 (= 20), 10 or 20.  y [N], m, v [N, dim_f]; cdf, sf [N], either may be NULL.
+ * Quantiles: q[n, i] for the nP <= HMOGP_QUANT_MAXP probabilities p[i]; a p outside (0, 1) gives NaN in its column.  Bernoulli and
+ * Ordinal: the smallest point of the support whose cdf is >= p, as a double.  The others: the y with cdf(y) = p -- solved on the cdf for
+ * p <= 1/2, on sf(y) = 1 - p otherwise; in y (Gaussian, HetGaussian) or in log y (Exponential, Weibull) -- by a bracketed Newton
+ * iteration whose loops are bounded at compile time: a row makes at most 128 evaluations of the rule, and is NaN when that budget is
+ * exhausted.  New symbols only: ABI version 8 stays.                                                                             */
+#define HMOGP_QUANT_MAXP 8
+int hmogp_predictive_cdf(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, const double* y, const double* m,
+                         const double* v, double* cdf /* [N] or NULL */, double* sf /* [N] or NULL */);
+int hmogp_predictive_quantile(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, int32_t nP,
+                              const double* p /* [nP] */, const double* m, const double* v, double* q /* [N, nP] */);
+/* The same for new rows of task t of an engine: q(f) at Xnew [Nnew, P] is formed on the device as hmogp_predict_f forms it (same
+ * chunks, same strict / default mode, small or regular model); the task's columns and |v| feed the kernels directly, with the task's
+ * CURRENT likelihood parameters and its private Ordinal table (hmogp_set_lik_params).  ynew is [Nnew] as above.  HMOGP_E_STATE
+ * before the first evaluation; HMOGP_E_INVALID for an unsupported family, a bad gh_T, nP outside 1 .. HMOGP_QUANT_MAXP, a NULL pointer
+ * (cdf / sf excepted) with Nnew > 0, a t out of range, or a bad Ordinal label -- every refusal before anything is launched.     */
+int hmogp_predict_cdf(hmogp_handle h, int32_t t, const double* Xnew, const double* ynew, int64_t Nnew, int32_t gh_T,
+                      double* cdf /* [Nnew] or NULL */, double* sf /* [Nnew] or NULL */);
+int hmogp_predict_quantile(hmogp_handle h, int32_t t, const double* Xnew, int64_t Nnew, int32_t nP, const double* p /* [nP] */,
+                           int32_t gh_T, double* q /* [Nnew, nP] */);
+
 /* Data generation on the device: one draw Y[n] ~ p(y | F[n, :]) per row with the link functions and clips of the
  * reference's `<likelihood>.samples` (het_likelihood.py:72-83 -> e.g. gamma.py:43-50, categorical.py:65-75; labels of
  * Categorical are 1..K).  Counter-based generator keyed by (seed, row): reproducible, but a different stream than

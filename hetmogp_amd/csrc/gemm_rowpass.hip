@@ -10,7 +10,9 @@
 //   * a branch-free main loop: full 128-column tiles and a k-extent that is a multiple of 16 are REQUIRED of the
 //     inducing dimension (gemm_rowpass_eligible; anything else takes the general kernel), ragged ROWS are handled by
 //     clamping the row index once per thread (forward) or by a zero k-scale (Gram), so a k-step is: 2-4 vector loads,
-//     32 MFMAs fed by 12 ds_read, 2-4 ds_write, one barrier -- no per-step bookkeeping.
+//     32 MFMAs fed by 12 ds_read, 2-4 ds_write, one barrier -- no per-step bookkeeping;
+//   * [r7] the plain forward (rowpass_gemm_kernel<1>) takes C_q's fragments straight from L2 into registers and spends the LDS on
+//     an A image of BK = 32: 64 MFMAs fed by 32 ds_read + 16 buffer loads, 4 ds_write, one barrier (see "B DIRECT" below).
 #include <cstdlib>
 
 #include "common.h"
@@ -20,6 +22,7 @@ namespace {
 constexpr int BM = 128, BN = 128, BK = 16, W = 8, NT = W * 64;
 constexpr int KM_LD = 144, RM_LD = 18, TILE_DOUBLES = BK * KM_LD;   // LDS images: see gemm_f64.hip
 constexpr int NB = 2, WN = 32, NWN = 4;                              // wave tile 64 x 32 = 4 x 2 sub-tiles; 4 wave columns
+constexpr int BK32 = 32, A32_LD = 34, BD_D = 2;                      // plain forward, B direct: A image at BK = 32, B ring depth
 
 struct Tile {
   double a[2][TILE_DOUBLES];
@@ -32,7 +35,7 @@ __device__ __forceinline__ int diag_wm(int w) { return (0x4B >> w) & 1; }
 __device__ __forceinline__ int diag_wn(int w) { return (0x7E84 >> (2 * w)) & 3; }
 
 // One 128 x 128 tile of the contraction: main loop + epilogue (everything the kernel does once it knows its tile).
-template <int ROLE, bool FOLD = false>
+template <int ROLE, bool FOLD = false, bool BD = false>
 __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int ti, int tj, int split, Tile& lds, double* epi_a,
                                              int* hwinfo = nullptr) {
   const int batch = blockIdx.z;
@@ -161,16 +164,121 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
       }
   };
 
+  // ---- [r7] plain forward, B DIRECT (BD): C_q's fragments straight from L2 into registers, A image at BK = 32 ---------------
+  // C_q is the one operand every block of the launch shares and its MFMA fragment is a coalesced access as it lies in memory
+  // (for a fixed k the 16 lanes lr read 16 adjacent doubles): registers -> ds_write -> ds_read was a copy.  Without the B image
+  // the LDS takes a double-buffered row-major A image of 128 x 32: ONE block barrier per 64 MFMAs per wave instead of one
+  // per 32.  tools/probes/probe_gemm_bdirect.hip, profiles/r07_gemm_bdirect.txt: 69.5 -> 71.5 TFLOP/s on the bare loop.
+  //   * A image: row stride A32_LD = 34 doubles.  A fragment read is one ds_read_b64 per lane at dword 68 lr + 2 lk (+ const):
+  //     68 lr mod 64 runs through the 16 multiples of 4, so the 32 lanes of a half wave (lk in {0, 1} / {2, 3}) hit 64 distinct
+  //     banks.  The stage writes are ds_write_b128: groups of 8 lanes, banks mod 32.  A thread writes the k's (t%4)*4..+3 and
+  //     16 + the same of row t/4 (as the staged loop does within its 16): per group 2 rows x 4 threads at dwords 0, 8, 16, 24
+  //     and 4 + the same (68 mod 32) -- conflict-free; 8 CONTIGUOUS k's per thread put threads 16 dwords apart: 2-way, measured
+  //     as SQ_LDS_BANK_CONFLICT 0.235 of the LDS cycles.  2 x 128 x 34 = 8704 doubles of the tile buffers' 9216; the epilogue's
+  //     staging needs 8192.
+  //   * B fragments: lane (lr, lk) of wave column wn loads B[(k + lk) ldb + j0 + 32 wn + 16 b + blr], b < 2, for the k4-step at
+  //     k, as two buffer_load_dwordx2 (lane part of the address in a VGPR that never changes, k ldb in an SGPR: no address
+  //     arithmetic on the vector pipe; the same loads with 64-bit lane addresses measured 69.6).  They run BD_D = 2 k4-steps
+  //     ahead of the MFMAs that consume them, in a ring of BD_D register slots: the loads of step s + BD_D are issued right
+  //     BEHIND the 8 MFMAs of step s, into the slot those have read.  (D = 2, 3, 4 measured 71.5, 71.0, 71.5: the shallowest.)
+  //   * waits: counted s_waitcnt vmcnt(n) on in-order return.  Every k4-step issues exactly its two B loads and every k-step
+  //     exactly its four A loads (beyond the last step they re-read the last one: clamped, never consumed), so in front of the
+  //     MFMAs of step s the loads issued AFTER B(s) are: B(s + 1) [2], and in the step behind the A loads those too [4]:
+  //     vmcnt(2) / vmcnt(6) can only be satisfied once B(s) has landed (vmcnt(3) / (7) for its first half).  The A loads are
+  //     older than every B fragment waited for from the third k4-step behind them on, so the stage of the next k-step needs
+  //     no wait of its own.  The compiler derives exactly these counts from the straight-line code (there is no conditional
+  //     load in the loop, which would make it fall back to the smaller count); they are not written by hand.
+  //   * same products in the same order per accumulator (k ascending, k4 grouping 4 kk + lk, operands swapped): P~, p and c are
+  //     bit-identical to the staged loop.
+  if constexpr (BD) {
+    static_assert(ROLE == 1 && !FOLD, "B direct: the plain forward only");
+    constexpr int KS = BK32 / 4, NA = BK32 / 4;
+    static_assert(KS % BD_D == 0, "static ring slots");
+    static_assert(2 * BM * A32_LD <= 4 * TILE_DOUBLES, "A image at BK = 32 fits the tile buffers");
+    double* const img = &lds.a[0][0];                          // [2][BM * A32_LD]
+    const int ar32 = t >> 2, ak32 = (t & 3) * 4;              // thread: row t/4, k's (t%4)*4..+3 and 16 + the same
+    const double* pa32 = A + (long long)min(i0 + ar32, M - 1) * g.lda + ak32;
+    double r32[NA];
+    auto load32 = [&](int k0) {
+      k0 = min(k0, kend - BK32);
+#pragma unroll
+      for (int i = 0; i < NA / 2; ++i) {
+        const f64x2 x = *reinterpret_cast<const f64x2*>(pa32 + k0 + (i >> 1) * 16 + (i & 1) * 2);
+        r32[2 * i] = x.x, r32[2 * i + 1] = x.y;
+      }
+    };
+    auto stage32 = [&](int buf) {
+      double* sa = img + buf * (BM * A32_LD) + ar32 * A32_LD + ak32;
+#pragma unroll
+      for (int i = 0; i < NA / 2; ++i) *reinterpret_cast<f64x2*>(sa + (i >> 1) * 16 + (i & 1) * 2) = f64x2{r32[2 * i], r32[2 * i + 1]};
+    };
+    // (launch_gemm_rowpass takes this loop only if the whole B panel is addressable with 32-bit byte offsets)
+    const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double*>(B), 0, (int)(sizeof(double) * ((long long)(K - 1) * g.ldb + N)), 0x00020000);
+    const int bvo = (int)sizeof(double) * (lk * g.ldb + j0 + wn * WN + blr);
+    double gb[BD_D][NB];
+    auto bload = [&](int k, int slot) {
+      const int so = __builtin_amdgcn_readfirstlane(min(k, kend - 4) * g.ldb * (int)sizeof(double));
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+        gb[slot][b] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(brs, bvo + b * 16 * (int)sizeof(double), so, 0));
+    };
+    double ga[2][4];
+    auto frag32 = [&](int buf, int kk, int s) {
+      const double* fpa = img + buf * (BM * A32_LD) + (wm * 64 + lr) * A32_LD + kk * 4 + lk;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ga[s][i] = fpa[i * 16 * A32_LD];
+    };
+    auto mm32 = [&](int s, int slot) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(gb[slot][b], ga[s][a], acc[a][b], 0, 0, 0);
+    };
+    int cur = 0;
+    if (kbeg < kend) {
+      load32(kbeg);
+      stage32(0);
+      load32(kbeg + BK32);
+#pragma unroll
+      for (int d = 0; d < BD_D; ++d) bload(kbeg + 4 * d, d);
+    }
+    __syncthreads();
+    if (kbeg < kend) frag32(0, 0, 0);
+    for (int k0 = kbeg; k0 < kend; k0 += BK32) {
+      const bool more = k0 + BK32 < kend;
+#pragma unroll
+      for (int kk = 0; kk < KS; ++kk) {
+        if (kk < KS - 1) {
+          frag32(cur, kk + 1, (kk + 1) & 1);
+        } else {                                               // (behind the last barrier of the tile no wave reads LDS any more)
+          __syncthreads();
+          if (more) frag32(cur ^ 1, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        mm32(kk & 1, kk % BD_D);
+        __builtin_amdgcn_sched_barrier(0);
+        bload(k0 + 4 * (kk + BD_D), kk % BD_D);
+        if (kk == 0) {
+          if (more) stage32(cur ^ 1);
+          load32(k0 + 2 * BK32);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      cur ^= 1;
+    }
+  }
+
   // Software pipeline: the operands of step k + 1 are in registers when step k starts; they are staged into the other LDS
   // buffer BEFORE the MFMA block of step k (so the ds_write latency is covered by it and the barrier follows the last MFMA
   // directly) and the registers are refilled at once with step k + 2.
   int cur = 0;
-  if (kbeg < kend) {
+  if (!BD && kbeg < kend) {
     load(kbeg);
     stage(0);
     if (kbeg + BK < kend) load(kbeg + BK);
   }
-  __syncthreads();
+  if (!BD) __syncthreads();
   if (diag) {
     int role = w;                                               // static assignment: pair type w & 3, half w >> 2
     if (hwinfo) {
@@ -218,9 +326,9 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
       cur ^= 1;
     }
   }
-  if (ROLE == 1 && kbeg < kend && (!FOLD || kbeg >= klive)) frag(0, 0, 0);
+  if (ROLE == 1 && !BD && kbeg < kend && (!FOLD || kbeg >= klive)) frag(0, 0, 0);
 #define HM_SB __builtin_amdgcn_sched_barrier(0)
-  for (int k0 = kbeg; ROLE == 1 && k0 < kend; k0 += BK) {
+  for (int k0 = kbeg; ROLE == 1 && !BD && k0 < kend; k0 += BK) {
     const bool more = k0 + BK < kend;
     const bool lv = !FOLD || k0 >= klive;                      // (wave-uniform; always true outside the fold's diagonal block)
     if (lv) {
@@ -373,7 +481,7 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
     }
 }
 
-template <int ROLE, bool PAIR>
+template <int ROLE, bool PAIR, bool BD = false>
 __device__ __forceinline__ void rowpass_block(const GemmArgs& g, int tiles_n, int ntiles, Tile& lds, double* epi_a,
                                               int* hwinfo = nullptr) {
 
@@ -419,7 +527,7 @@ __device__ __forceinline__ void rowpass_block(const GemmArgs& g, int tiles_n, in
     ti = v / tcols;
     tj = v - ti * tcols;
   }
-  rowpass_tile<ROLE, PAIR>(g, tiles_n, ti, tj, split, lds, epi_a, hwinfo);
+  rowpass_tile<ROLE, PAIR, BD>(g, tiles_n, ti, tj, split, lds, epi_a, hwinfo);
   // Triangular fold (b_tri > 0, the E-step's / predict_f's forward): the k-loop of column tile j starts at j, so the tiles of
   // a row panel do 8, 7, ... 1 eighths of a full tile's work.  In paired mode a block takes column tiles j and
   // tiles_n - 1 - j one after the other: every block does (tiles_n + 1) / tiles_n of a full tile -- equal durations.
@@ -435,7 +543,14 @@ __global__ __launch_bounds__(NT, 4) void rowpass_gemm_kernel(GemmArgs g, int til
   __shared__ __attribute__((aligned(16))) Tile lds;
   __shared__ __attribute__((aligned(16))) double epi_a[ROLE == 1 ? 128 : 2];
   __shared__ int hwinfo[ROLE == 2 ? 16 : 1];
-  rowpass_block<ROLE, false>(g, tiles_n, ntiles, lds, epi_a, ROLE == 2 ? hwinfo : nullptr);
+  rowpass_block<ROLE, false, ROLE == 1>(g, tiles_n, ntiles, lds, epi_a, ROLE == 2 ? hwinfo : nullptr);   // (forward: B direct)
+}
+// the forward contraction with BOTH operands staged through LDS (BK = 16): the C -= A B updates of the strict solves (k-extents
+// that are multiples of 16 only), the unpaired triangular fold, B panels beyond 32-bit byte offsets
+__global__ __launch_bounds__(NT, 4) void rowpass_fwd_staged_kernel(GemmArgs g, int tiles_n, int ntiles) {
+  __shared__ __attribute__((aligned(16))) Tile lds;
+  __shared__ __attribute__((aligned(16))) double epi_a[128];
+  rowpass_block<1, false>(g, tiles_n, ntiles, lds, epi_a);
 }
 // the forward contraction against the triangular fold of C, two column tiles per block (see rowpass_block)
 __global__ __launch_bounds__(NT, 4) void rowpass_fold_pair_kernel(GemmArgs g, int tiles_n, int ntiles) {
@@ -481,8 +596,11 @@ void launch_gemm_rowpass(const GemmArgs& g_in, hipStream_t stream) {
     if (pair) {
       grid.x = tiles_m * (tiles_n / 2);
       hipLaunchKernelGGL(rowpass_fold_pair_kernel, grid, dim3(NT), 0, stream, g, tiles_n, (int)grid.x);
-    } else {
+    } else if (!g.c_sub && g.b_tri == 0 && (g.K % BK32) == 0 && ((long long)(g.K - 1) * g.ldb + g.N) * (long long)sizeof(double) <= 0x7FFFFFFFLL) {
+      // plain forward: C_q's fragments straight from L2, A image at BK = 32 (needs k-extent % 32 == 0: holds whenever K == N)
       hipLaunchKernelGGL((rowpass_gemm_kernel<1>), grid, dim3(NT), 0, stream, g, tiles_n, ntiles);
+    } else {
+      hipLaunchKernelGGL(rowpass_fwd_staged_kernel, grid, dim3(NT), 0, stream, g, tiles_n, ntiles);
     }
   } else {
     hipLaunchKernelGGL((rowpass_gemm_kernel<2>), grid, dim3(NT), 0, stream, g, tiles_n, ntiles);

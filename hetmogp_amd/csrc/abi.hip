@@ -41,6 +41,11 @@ void upload_y(int lik_id, double lik_param, const double* y, long long N, DevBuf
   upload_y_image(lik_id, lik_param, nullptr, y, N, dy);
 }
 
+// Binomial, Beta-Binomial: the trial count n* is refused on the host, before the device is asked for (the same answer with or without one)
+void check_trials_first(int lik_id, double lik_param) {
+  if (lik_id == HMOGP_LIK_BINOMIAL || lik_id == HMOGP_LIK_BETABINOMIAL) check_lik_param(lik_id, lik_param);
+}
+
 }  // namespace
 
 namespace hmogp_detail {
@@ -48,6 +53,7 @@ namespace hmogp_detail {
 // ([2][N], what launch_var_exp / launch_log_predictive read), so that the device code is the engine's.  Dirichlet: y is [N][K]; it is
 // checked and replaced by log y_k as [K][N], the engine's layout.  Negative Binomial: the counts are checked and uploaded as they are.
 // Weibull: y is [N][2] = (y, delta); it is checked and replaced by (log y, delta) as [2][N], the engine's layout.
+// Binomial, Beta-Binomial: y is [N][2] = (k, n); it is checked and replaced by (k, n, lc) as [3][N].
 // `tb`: the Ordinal table to cut by instead of the registry entry `lik_param` names (a task's private table).
 void upload_y_image(int lik_id, double lik_param, const OrdinalTable* tb, const double* y, long long N, DevBuf& dy) {
   if (lik_id == HMOGP_LIK_WEIBULL) {
@@ -55,6 +61,13 @@ void upload_y_image(int lik_id, double lik_param, const OrdinalTable* tb, const 
     weibull_check_rows(y, N, img.data());
     dy.ensure(sizeof(double) * 2 * N);
     HIP_TRY(hipMemcpy(dy.p, img.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
+    return;
+  }
+  if (lik_id == HMOGP_LIK_BINOMIAL || lik_id == HMOGP_LIK_BETABINOMIAL) {
+    std::vector<double> img(3 * (size_t)N);
+    binomial_check_rows(lik_id, y, N, img.data());
+    dy.ensure(sizeof(double) * 3 * N);
+    HIP_TRY(hipMemcpy(dy.p, img.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
     return;
   }
   if (lik_id == HMOGP_LIK_DIRICHLET) {
@@ -470,6 +483,7 @@ int hmogp_var_exp(int32_t device, int32_t lik_id, double lik_param, int64_t N, c
 int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t quirks, int64_t N, const double* y,
                      const double* m, const double* v, double* ve, double* dm, double* dv) {
   return guarded(nullptr, [&] {
+    check_trials_first(lik_id, lik_param);
     need_device(device);
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);
@@ -493,6 +507,7 @@ int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t 
 int hmogp_var_exp_dparam(int32_t device, int32_t lik_id, double lik_param, int64_t N, const double* y, const double* m,
                          const double* v, double* out) {
   return guarded(nullptr, [&] {
+    check_trials_first(lik_id, lik_param);
     need_device(device);
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);
@@ -538,6 +553,7 @@ int hmogp_ordinal_table(int32_t K, const double* edges, double sigma, double* li
 int hmogp_predictive(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, const double* m,
                      const double* v, double* mean, double* var) {
   return guarded(nullptr, [&] {
+    check_trials_first(lik_id, lik_param);
     need_device(device);
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);
@@ -561,6 +577,7 @@ int hmogp_predictive(int32_t device, int32_t lik_id, double lik_param, int32_t g
 int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64_t N, int32_t num_samples, uint64_t seed,
                          const double* y, const double* m, const double* v, double* log_pred) {
   return guarded(nullptr, [&] {
+    check_trials_first(lik_id, lik_param);
     need_device(device);
     const int J = lik_dimf(lik_id, lik_param);
     check_lik_param(lik_id, lik_param);
@@ -592,6 +609,7 @@ static int lpd_nodes(int lik_id, int gh_T) {
 int hmogp_log_predictive_gh(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, const double* y,
                             const double* m, const double* v, double* lpd, double* ess) {
   return guarded(nullptr, [&] {
+    check_trials_first(lik_id, lik_param);
     need_device(device);
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);
@@ -705,12 +723,13 @@ int hmogp_predict_quantile(hmogp_handle h, int32_t t, const double* Xnew, int64_
 
 int hmogp_sample(int32_t device, int32_t lik_id, double lik_param, int64_t N, uint64_t seed, const double* F, double* Y) {
   return guarded(nullptr, [&] {
+    check_trials_first(lik_id, lik_param);
     need_device(device);
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);
     check_lik_param(lik_id, lik_param);
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !F || !Y) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
-    const int Jy = lik_id == HMOGP_LIK_DIRICHLET ? J : 1;   // columns of Y (Weibull: event times only, one column)
+    const int Jy = lik_id == HMOGP_LIK_DIRICHLET ? J : 1;   // columns of Y (Weibull: event times only; Binomial, Beta-Binomial: counts only)
     DevBuf dF, dY;
     dF.ensure(sizeof(double) * N * J), dY.ensure(sizeof(double) * N * Jy);
     HIP_TRY(hipMemcpy(dF.p, F, sizeof(double) * N * J, hipMemcpyHostToDevice));

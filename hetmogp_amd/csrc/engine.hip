@@ -184,6 +184,10 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
     cuts.resize(2 * (size_t)N);
     weibull_check_rows(Y, N, cuts.data());
   }
+  if ((k.lik == HMOGP_LIK_BINOMIAL || k.lik == HMOGP_LIK_BETABINOMIAL) && N > 0) {   // Y is [N, 2] = (k, n); checked, and (k, n, lc) laid out
+    cuts.resize(3 * (size_t)N);                                                      // [3][N], before the state changes
+    binomial_check_rows(k.lik, Y, N, cuts.data());
+  }
   k.N = N;
   began = false;
   staged_key.clear();
@@ -206,6 +210,11 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
   if (k.lik == HMOGP_LIK_WEIBULL) {   // log y depends on the data only, like gammaln(y+1) above
     k.Ylo.ensure(sizeof(double) * 2 * N);
     HIP_TRY(hipMemcpy(k.Ylo.p, cuts.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
+  }
+  if (k.lik == HMOGP_LIK_BINOMIAL || k.lik == HMOGP_LIK_BETABINOMIAL) {   // lc depends on the data only, like gammaln(y+1) above
+    k.Ylo.ensure(sizeof(double) * 2 * N), k.Yaux.ensure(sizeof(double) * N);
+    HIP_TRY(hipMemcpy(k.Ylo.p, cuts.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k.Yaux.p, cuts.data() + 2 * N, sizeof(double) * N, hipMemcpyHostToDevice));
   }
   if (k.lik == HMOGP_LIK_DIRICHLET) {
     k.Ylo.ensure(sizeof(double) * N * k.dimf);

@@ -105,10 +105,12 @@ struct Task {
   int lik = 0, dimf = 1, d0 = 0;
   double param = 0.0;
   double qparam = 0.0;   // what the quadrature kernels get as lik_param: `param`, but sigma for Ordinal (whose param is a table id)
-  // Weibull: Ylo is the [2][N] image (log y, delta) of the task's [N, 2] Y
-  const double* quad_y() const { return (lik == HMOGP_LIK_ORDINAL || lik == HMOGP_LIK_DIRICHLET || lik == HMOGP_LIK_WEIBULL) ? Ylo.d() : Y.d(); }   // first per-row value of the quadrature
-  long long quad_ldy() const { return (lik == HMOGP_LIK_DIRICHLET || lik == HMOGP_LIK_WEIBULL) ? N : 0; }   // row stride of quad_y() where a row has several values (QuadArgs::ldy)
-  int dimy() const { return lik == HMOGP_LIK_DIRICHLET ? dimf : (lik == HMOGP_LIK_WEIBULL ? 2 : 1); }   // columns of the task's Y
+  // Weibull: Ylo is the [2][N] image (log y, delta) of the task's [N, 2] Y.  Binomial, Beta-Binomial: Ylo is the
+  // [2][N] image (k, n) of the task's [N, 2] Y and Yaux holds lc = lgamma(n+1) - lgamma(k+1) - lgamma(n-k+1)
+  bool two_col() const { return lik == HMOGP_LIK_WEIBULL || lik == HMOGP_LIK_BINOMIAL || lik == HMOGP_LIK_BETABINOMIAL; }
+  const double* quad_y() const { return (lik == HMOGP_LIK_ORDINAL || lik == HMOGP_LIK_DIRICHLET || two_col()) ? Ylo.d() : Y.d(); }   // first per-row value of the quadrature
+  long long quad_ldy() const { return (lik == HMOGP_LIK_DIRICHLET || two_col()) ? N : 0; }   // row stride of quad_y() where a row has several values (QuadArgs::ldy)
+  int dimy() const { return lik == HMOGP_LIK_DIRICHLET ? dimf : (two_col() ? 2 : 1); }   // columns of the task's Y
   DevBuf offsets;  // device: quad scalar slot -> bundle offset
   int nscal = 0;
   // Ordinal, after hmogp_set_lik_params: the task's PRIVATE table replaces the registry entry `param` names
@@ -144,6 +146,9 @@ void dirichlet_log_rows(int K, const double* y, long long N, double* ly);
 void negbinomial_check_rows(const double* y, long long N);   // HMOGP_E_INVALID unless every y is a finite, non-negative integer
 // Weibull: rows (y, delta) [N][2] (y finite and > 0, delta exactly 0 or 1, else HMOGP_E_INVALID) -> img [2][N] = log y, delta
 void weibull_check_rows(const double* y, long long N, double* img);
+// Binomial / Beta-Binomial: rows (k, n) [N][2] (integers, 1 <= n <= 1e9, 0 <= k <= n, else HMOGP_E_INVALID with the family's name) ->
+// img [3][N] = k, n, lc = lgamma(n+1) - lgamma(k+1) - lgamma(n-k+1)
+void binomial_check_rows(int lik, const double* y, long long N, double* img);
 // Ordinal: labels y [N] (integers in 1..K, else HMOGP_E_INVALID) -> the rows' lower / upper cut points (-inf / +inf at the ends)
 void ordinal_row_cuts(const OrdinalTable& tb, const double* y, long long N, double* lo, double* hi);
 // registers (or finds) a table; returns the value to pass as lik_param

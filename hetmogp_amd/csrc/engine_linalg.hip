@@ -14,13 +14,15 @@ int lik_dimf(int lik, double param) {
     case HMOGP_LIK_BERNOULLI:
     case HMOGP_LIK_POISSON:
     case HMOGP_LIK_EXPONENTIAL:
-    case HMOGP_LIK_ORDINAL: return 1;
+    case HMOGP_LIK_ORDINAL:
+    case HMOGP_LIK_BINOMIAL: return 1;
     case HMOGP_LIK_HETGAUSSIAN:
     case HMOGP_LIK_GAMMA:
     case HMOGP_LIK_BETA:
     case HMOGP_LIK_STUDENT:
     case HMOGP_LIK_NEGBINOMIAL:
-    case HMOGP_LIK_WEIBULL: return 2;
+    case HMOGP_LIK_WEIBULL:
+    case HMOGP_LIK_BETABINOMIAL: return 2;
     case HMOGP_LIK_CATEGORICAL: return (int)param - 1;
     case HMOGP_LIK_DIRICHLET: return (param >= 2.0 && param <= (double)HMOGP_DIRICHLET_MAXK) ? (int)param : -1;
     default: return -1;
@@ -33,6 +35,28 @@ void check_lik_param(int lik, double param) {
   if (lik == HMOGP_LIK_ORDINAL) (void)ordinal_table(param);
   if (lik == HMOGP_LIK_DIRICHLET && !(param >= 2.0 && param <= (double)HMOGP_DIRICHLET_MAXK && param == std::floor(param)))
     throw EngineError{HMOGP_E_INVALID, "Dirichlet: K must be an integer in 2 .. HMOGP_DIRICHLET_MAXK"};
+  // Binomial, Beta-Binomial: the trial count n* of predictive / sample; 0.0 means 1
+  if ((lik == HMOGP_LIK_BINOMIAL || lik == HMOGP_LIK_BETABINOMIAL) && param != 0.0 &&
+      !(param >= 1.0 && param <= 1e9 && param == std::floor(param)))
+    throw EngineError{HMOGP_E_INVALID, lik == HMOGP_LIK_BINOMIAL ? "Binomial: the trial count n* (lik_param) must be an integer in 1 .. 1e9, or 0 for 1"
+                                                                 : "BetaBinomial: the trial count n* (lik_param) must be an integer in 1 .. 1e9, or 0 for 1"};
+}
+
+// ------------------------------------------------------------------------------------ Binomial / Beta-Binomial rows
+void binomial_check_rows(int lik, const double* y, long long N, double* img) {
+  const bool bb = lik == HMOGP_LIK_BETABINOMIAL;
+  for (long long i = 0; i < N; ++i) {
+    const double k = y[2 * i], n = y[2 * i + 1];
+    if (!(std::isfinite(n) && n >= 1.0 && n <= 1e9 && n == std::floor(n)))
+      throw EngineError{HMOGP_E_INVALID, bb ? "BetaBinomial: every trial count n must be an integer in 1 .. 1e9"
+                                            : "Binomial: every trial count n must be an integer in 1 .. 1e9"};
+    if (!(std::isfinite(k) && k >= 0.0 && k <= n && k == std::floor(k)))
+      throw EngineError{HMOGP_E_INVALID, bb ? "BetaBinomial: every count k must be an integer in 0 .. n"
+                                            : "Binomial: every count k must be an integer in 0 .. n"};
+    img[i] = k;
+    img[N + i] = n;
+    img[2 * N + i] = std::lgamma(n + 1.0) - std::lgamma(k + 1.0) - std::lgamma(n - k + 1.0);
+  }
 }
 
 // ------------------------------------------------------------------------------------ Negative Binomial rows

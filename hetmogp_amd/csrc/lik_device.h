@@ -7,7 +7,8 @@
 //   Q1  Gamma / Beta: Gauss-Hermite weights divided by sqrt(pi) twice (gamma.py:110,139-141; beta.py:113,142-144)
 //   Q2  Categorical: d/dm is the constant onehot(y)[d] - 1 (categorical.py:102-113)
 // At the end of the file: the derivatives with respect to the likelihoods' OWN parameters (Gaussian sigma, Student nu, Ordinal cut
-// points and sigma), appended so that nothing above them changes.
+// points and sigma), appended so that nothing above them changes; and, appended last, the Binomial and Beta-Binomial families
+// with per-row trial counts (one lane per row and one wave per row).
 // Lane mapping: closed forms, 1-D quadratures and Gamma (separable in its two functions) use ONE lane per row;
 // Beta (100 nodes), Student, Negative Binomial and Weibull (400 nodes), Categorical (10^(K-1) nodes) and Dirichlet (10^K nodes) use ONE WAVE per row,
 // nodes strided over the 64 lanes and reduced with wavefront shuffles.
@@ -27,6 +28,16 @@ struct LikOut {
   double gm[HMOGP_MAXJ];
   double gv[HMOGP_MAXJ];
 };
+
+// Binomial / Beta-Binomial: defined in the last section of this file, declared here for the dispatchers in between
+__device__ __forceinline__ void lik_binomial_quad(double k, double n, double lc, double m, double v, LikOut& o);
+__device__ __forceinline__ void lik_betabinomial_wave(double k, double n, double lc, const double* m, const double* v, int lane,
+                                                      double* tab, LikOut& o);
+__device__ __forceinline__ double lik_binomial_logpdf(double k, double n, double lc, const double* f);
+__device__ __forceinline__ double lik_betabinomial_logpdf(double k, double n, double lc, const double* f);
+__device__ __forceinline__ void lik_binomial_predictive(double m, double v, double param, int T, double& mean, double& var);
+__device__ __forceinline__ void lik_betabinomial_predictive(const double* m, const double* v, double param, int T, double& mean,
+                                                            double& var);
 
 __device__ __forceinline__ double safe_exp(double f) { return exp(fmin(f, LIM_VAL)); }
 __device__ __forceinline__ double safe_square(double f) {
@@ -229,7 +240,8 @@ __device__ __forceinline__ void lik_ordinal_predictive(const OrdinalTable& tb, d
 // Student [0,60) r_i = y - f0(node i), f1(node j), s_j = exp(-f1(node j)); Dirichlet [0,40) a_k(node i), [40,50) weights,
 // [56,64) m_k, v_k (predictive, T = 20: [0,80) a_k(node i), [80,88) m_k, v_k); Negative Binomial [0,20) min(f0(node i), LIM_VAL), then
 // per node j of f1: [20,40) log r_j, [40,60) r_j, [60,80) G_j - lgamma(y+1), [80,100) r_j D1_j, [100,120) r_j^2 D2_j;
-// Weibull [0,20) log y - f0(node i), [20,40) k_j, [40,60) log k_j.
+// Weibull [0,20) log y - f0(node i), [20,40) k_j, [40,60) log k_j; Beta-Binomial [0,80) a_i, G(k, a_i), a_i D1(k, a_i), a_i^2 D2(k, a_i),
+// [80,160) the same four for b_j with n - k.
 #define HMOGP_ETAB 176
 
 __device__ __forceinline__ double wave_min(double v) {
@@ -476,7 +488,8 @@ __device__ __forceinline__ double nb_stirling_e(double x) {  // psi'(x) - 1/x - 
   return ix * z *
          (1.0 / 6.0 + z * (-1.0 / 30.0 + z * (1.0 / 42.0 + z * (-1.0 / 30.0 + z * (5.0 / 66.0 + z * (-691.0 / 2730.0 + z * (7.0 / 6.0)))))));
 }
-// y: a non-negative integer-valued double (checked on the host), r in [1e-9, 1e9]
+// y: a non-negative integer-valued double (checked on the host), r in [1e-9, 1e9]; the Beta-Binomial also calls it with
+// r = a + b up to 2e9 and y up to 1e9: the y <= 32 product then reaches (2e9 + 31)^32 = 4e297, still finite, and the series are unaffected
 __device__ __forceinline__ void nb_gamma_diffs(double y, double r, double& G, double& D1, double& D2) {
   if (y <= 32.0) {
     const int ny = (int)y;
@@ -978,6 +991,10 @@ __device__ __forceinline__ void lik_predictive(const double* m, const double* v,
     var[0] = mu + exp(2.0 * m[0] + 2.0 * v[0] - m[1] + 0.5 * v[1]) + (v[0] > 0.0 ? expm1(v[0]) * exp(2.0 * m[0] + v[0]) : 0.0);
   } else if (LIK == HMOGP_LIK_WEIBULL) {  // one lane per row, GH20 over f1
     lik_weibull_predictive(m, v, mean[0], var[0]);
+  } else if (LIK == HMOGP_LIK_BINOMIAL) {  // one lane per row, param = the trial count n*
+    lik_binomial_predictive(m[0], v[0], param, T, mean[0], var[0]);
+  } else if (LIK == HMOGP_LIK_BETABINOMIAL) {
+    lik_betabinomial_predictive(m, v, param, T, mean[0], var[0]);
   } else {  // Categorical, categorical.py:84-99,224-269: E[rho_d], rho normalised over the K-1 columns; variance zeros
     const int D = (int)param - 1;
     for (int e = lane; e < D * 10; e += 64) {
@@ -1141,6 +1158,10 @@ __device__ __forceinline__ double lik_logpdf_sample(double y, double yaux, const
     return lik_negbinomial_logpdf(y, yaux, f);
   } else if (LIK == HMOGP_LIK_WEIBULL) {  // y = log of the time, yaux = delta
     return lik_weibull_logpdf(y, yaux, f);
+  } else if (LIK == HMOGP_LIK_BINOMIAL) {  // y = k, yaux = lc, param = the row's own trial count n
+    return lik_binomial_logpdf(y, param, yaux, f);
+  } else if (LIK == HMOGP_LIK_BETABINOMIAL) {
+    return lik_betabinomial_logpdf(y, param, yaux, f);
   }
   return nan("");
 }
@@ -1218,6 +1239,7 @@ struct RowRng {
     }
     return floor(lam);
   }
+  __device__ double binomial(double n, double p);  // DESIGN 9l; defined in the last section of this file
 };
 
 template <int LIK>
@@ -1248,6 +1270,15 @@ __device__ __forceinline__ double lik_sample(RowRng& g, const double* f, double 
     return g.poisson(safe_exp(f[0]) * g.gamma(r) / r);
   } else if (LIK == HMOGP_LIK_WEIBULL) {  // inversion of the survival function: an event time, never censored
     return safe_exp(f[0]) * pow(-log(g.uniform()), 1.0 / weibull_shape(f[1]));
+  } else if (LIK == HMOGP_LIK_BINOMIAL) {  // param = the trial count n* (0: 1)
+    const double ef = safe_exp(f[0]);
+    return g.binomial(param > 0.0 ? param : 1.0, clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9));
+  } else if (LIK == HMOGP_LIK_BETABINOMIAL) {  // Beta's own draw p = Gamma_a / (Gamma_a + Gamma_b), then Binomial(n*, p)
+    const double a = clip(safe_exp(f[0]), 1e-9, 1e9), b = clip(safe_exp(f[1]), 1e-9, 1e9);
+    const double x = g.gamma(a), yv = g.gamma(b);
+    // (both variates underflow where a and b are tiny: the mass sits on p = 0 and p = 1, p = 1 with probability a / (a + b))
+    const double p = x + yv > 0.0 ? x / (x + yv) : (g.uniform() * (a + b) < a ? 1.0 : 0.0);
+    return g.binomial(param > 0.0 ? param : 1.0, p);
   } else {  // Categorical: labels 1..K, probabilities clipped then renormalised (categorical.py:66-71)
     const int K = (int)param, D = K - 1;
     double e[HMOGP_MAXJ], esum = 0.0;
@@ -1322,7 +1353,7 @@ __host__ __device__ constexpr int lik_pred_lanes(int lik) {
 // lanes per row of a likelihood
 __host__ __device__ constexpr int lik_lanes(int lik) {
   return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_STUDENT || lik == HMOGP_LIK_DIRICHLET ||
-          lik == HMOGP_LIK_NEGBINOMIAL || lik == HMOGP_LIK_WEIBULL)
+          lik == HMOGP_LIK_NEGBINOMIAL || lik == HMOGP_LIK_WEIBULL || lik == HMOGP_LIK_BETABINOMIAL)
              ? 64
              : 1;
 }
@@ -1352,6 +1383,10 @@ __device__ __forceinline__ void lik_eval(double y, double yaux, const double* m,
     lik_negbinomial_wave(y, yaux, m, v, lane, etab, o);   // yaux: lgamma(y + 1)
   else if (LIK == HMOGP_LIK_WEIBULL)
     lik_weibull_wave(y, yaux, m, v, lane, etab, o);   // y: log of the time, yaux: delta
+  else if (LIK == HMOGP_LIK_BINOMIAL)
+    lik_binomial_quad(y, param, yaux, m[0], v[0], o);   // y: k, param: the row's own trial count n, yaux: lc
+  else if (LIK == HMOGP_LIK_BETABINOMIAL)
+    lik_betabinomial_wave(y, param, yaux, m, v, lane, etab, o);
   else
     lik_categorical_t<(CATD > 0 ? CATD : 1)>(y, m, v, lane, etab, quirks, o);
   if ((LIK == HMOGP_LIK_GAMMA || LIK == HMOGP_LIK_BETA) && !(quirks & HMOGP_QUIRK_GAMMA_BETA_PI)) {
@@ -1525,4 +1560,177 @@ __device__ __forceinline__ void lik_cdf_sf(double y, double yaux, const double* 
   } else {
     C = S = nan("");
   }
+}
+
+// ============================================================================ Binomial and Beta-Binomial
+// k successes out of n trials, n the row's own: Y is (k, n) per row, both integer-valued doubles with 1 <= n <= 1e9, 0 <= k <= n (checked
+// on the host), and lc = lgamma(n+1) - lgamma(k+1) - lgamma(n-k+1) is formed once per row on the host, as gammaln(y+1) is for Poisson.
+// The dispatchers above hand the row over as (y, param, yaux) = (k, n, lc): the task's lik_param is the trial count n* of `predictive` and
+// `sample` only (no y reaches them) and is ignored wherever y carries n.  Appended, like the sections above, so that nothing in front changes.
+__host__ __device__ constexpr bool lik_has_trials(int lik) { return lik == HMOGP_LIK_BINOMIAL || lik == HMOGP_LIK_BETABINOMIAL; }
+__device__ __forceinline__ double lik_pred_trials(double param) { return param > 0.0 ? param : 1.0; }   // 0.0 means 1 (checked on the host)
+
+// ---- Binomial, T = 20, one lane per row.  Bernoulli's link and clip, p = clip(e^f / (1 + e^f), 1e-9, 1 - 1e-9), and its expression shapes:
+//   lp = lc + k log p + (n - k) log(1 - p)      d1 = ((k - n p) / (1 - p)) (1 / (1 + e^f))      d2 = -(n p) / (1 + e^f)
+// so that a row (k, n) is n Bernoulli rows collapsed into one, and at n = 1 (lc = 0, k and n - k one of them 0 and the other 1: every product
+// with them is exact) each operation is lik_quad1d<BERNOULLI>'s on the same operands.  A loop of its own: the three instantiations of
+// lik_quad1d keep their code.
+__device__ __forceinline__ void lik_binomial_quad(double k, double n, double lc, double m, double v, LikOut& o) {
+  const double s = sqrt(2.0 * v), nk = n - k;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma unroll 4
+  for (int i = 0; i < 20; ++i) {
+    const double f = GH20_X[i] * s + m, w = GH20_WN[i];
+    const double ef = safe_exp(f);
+    const double p = clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9);
+    const double lp = (k * log(p) + nk * log(1.0 - p)) + lc;
+    const double d1 = ((k - n * p) / (1.0 - p)) * (1.0 / (1.0 + ef));
+    const double d2 = -(n * p) / (1.0 + ef);
+    a0 += lp * w;
+    a1 += d1 * w;
+    a2 += d2 * w;
+  }
+  o.ve = a0;
+  o.gm[0] = a1;
+  o.gv[0] = 0.5 * a2;
+}
+
+// The full log p at one f (Monte-Carlo and deterministic log predictive)
+__device__ __forceinline__ double lik_binomial_logpdf(double k, double n, double lc, const double* f) {
+  const double ef = safe_exp(f[0]);
+  const double p = clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9);
+  return (k * log(p) + (n - k) * log(1.0 - p)) + lc;
+}
+
+// mean = n* E[p],  var = n* E[p (1 - p)] + n*^2 (E[p^2] - E[p]^2) over the T nodes.  The second term is the variance of p under the rule,
+// formed in a second pass as sum w (p - E[p])^2: as a difference of two numbers of order one it would carry n*^2 eps, n* eps of the result.
+__device__ __forceinline__ void lik_binomial_predictive(double m, double v, double param, int T, double& mean, double& var) {
+  const double s = sqrt(2.0 * v), nt = lik_pred_trials(param);
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  for (int i = 0; i < T; ++i) {
+    const double ef = safe_exp(gh_x(T, i) * s + m), w = gh_wn(T, i);
+    const double p = clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9);
+    a0 += p * w;
+    a1 += p * (1.0 - p) * w;
+  }
+  for (int i = 0; i < T; ++i) {
+    const double ef = safe_exp(gh_x(T, i) * s + m), w = gh_wn(T, i);
+    const double d = clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9) - a0;
+    a2 += d * d * w;
+  }
+  mean = nt * a0;
+  var = nt * a1 + nt * nt * a2;
+}
+
+// ---- Beta-Binomial, 20 x 20, one wave per row.  Beta's links and clips, a = clip(safe_exp(f0), 1e-9, 1e9), b likewise, s = a + b.  With
+// G(y, r) = lgamma(y+r) - lgamma(r), D1 = psi(y+r) - psi(r), D2 = psi'(y+r) - psi'(r) -- nb_gamma_diffs' three regimes, never the plain
+// difference of two large numbers (s <= 2e9: the y <= 32 product stays below 1e298) --
+//   log p    = lc + G(k, a) + G(n-k, b) - G(n, s)
+//   d/df0    = a [D1(k, a) - D1(n, s)]           d2/df0^2 = d/df0 + a^2 [D2(k, a) - D2(n, s)]
+//   d/df1    = b [D1(n-k, b) - D1(n, s)]         d2/df1^2 = d/df1 + b^2 [D2(n-k, b) - D2(n, s)]      (the clips are ignored, as for Beta)
+// Only the three functions of s couple the dimensions (alpha = exp f keeps the tables separable; a mean / precision pair would not): lanes
+// 0-19 write a_i, G(k, a_i), a_i D1(k, a_i), a_i^2 D2(k, a_i) into the wave's LDS slice, lanes 20-39 the same four for b_j with n - k.
+// Each of the 400 nodes then costs one nb_gamma_diffs(n, a_i + b_j); n is the same in the whole wave, so its y <= 32 loop does not
+// diverge, and beyond it the r >= 16 / r < 16 branch is taken per lane, both sides bounded.
+__device__ __forceinline__ void lik_betabinomial_wave(double k, double n, double lc, const double* m, const double* v, int lane,
+                                                      double* tab, LikOut& o) {
+  static_assert(160 <= HMOGP_ETAB, "Beta-Binomial table");
+  if (lane < 40) {
+    const int dim = lane / 20, i = lane - 20 * dim;
+    const double x = clip(safe_exp(GH20_X[i] * sqrt(2.0 * (dim == 0 ? v[0] : v[1])) + (dim == 0 ? m[0] : m[1])), 1e-9, 1e9);
+    double G, D1, D2;
+    nb_gamma_diffs(dim == 0 ? k : n - k, x, G, D1, D2);
+    double* t = tab + 80 * dim + i;
+    t[0] = x, t[20] = G, t[40] = x * D1, t[60] = x * x * D2;
+  }
+  __builtin_amdgcn_wave_barrier();  // written and read by this wave only (LDS operations of a wave are in order)
+  double ve = 0.0, g0 = 0.0, g1 = 0.0, h0 = 0.0, h1 = 0.0;
+  for (int nd = lane; nd < 400; nd += 64) {
+    const int i = nd / 20, j = nd - 20 * i;
+    const double w = GH20_WN[i] * GH20_WN[j];
+    const double a = tab[i], b = tab[80 + j];
+    double G, D1, D2;
+    nb_gamma_diffs(n, a + b, G, D1, D2);
+    const double d0 = tab[40 + i] - a * D1, d1 = tab[120 + j] - b * D1;
+    ve += w * (lc + tab[20 + i] + tab[100 + j] - G);
+    g0 += w * d0;
+    g1 += w * d1;
+    h0 += w * (d0 + (tab[60 + i] - a * a * D2));
+    h1 += w * (d1 + (tab[140 + j] - b * b * D2));
+  }
+  o.ve = wave_sum(ve);
+  o.gm[0] = wave_sum(g0);
+  o.gm[1] = wave_sum(g1);
+  o.gv[0] = 0.5 * wave_sum(h0);
+  o.gv[1] = 0.5 * wave_sum(h1);
+}
+
+__device__ __forceinline__ double lik_betabinomial_logpdf(double k, double n, double lc, const double* f) {
+  const double a = clip(safe_exp(f[0]), 1e-9, 1e9), b = clip(safe_exp(f[1]), 1e-9, 1e9);
+  return lc + nb_lgamma_diff(k, a) + nb_lgamma_diff(n - k, b) - nb_lgamma_diff(n, a + b);
+}
+
+// With mu = a / s over the T x T nodes (one lane per row; b_j is formed again per node rather than kept in an indexed array):
+//   mean = n* E[mu],  var = n* E[mu (1 - mu) (s + n*) / (s + 1)] + n*^2 (E[mu^2] - E[mu]^2),   the last term in a second pass, as above
+__device__ __forceinline__ void lik_betabinomial_predictive(const double* m, const double* v, double param, int T, double& mean,
+                                                            double& var) {
+  const double s0 = sqrt(2.0 * v[0]), s1 = sqrt(2.0 * v[1]), nt = lik_pred_trials(param);
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma unroll 1
+  for (int pass = 0; pass < 2; ++pass) {
+    const double e1 = a0;   // (complete in the second pass)
+    for (int i = 0; i < T; ++i) {
+      const double a = clip(safe_exp(gh_x(T, i) * s0 + m[0]), 1e-9, 1e9), wi = gh_wn(T, i);
+#pragma unroll 1
+      for (int j = 0; j < T; ++j) {
+        const double b = clip(safe_exp(gh_x(T, j) * s1 + m[1]), 1e-9, 1e9), w = wi * gh_wn(T, j);
+        const double s = a + b, mu = a / s;
+        if (pass == 0) {
+          a0 += w * mu;
+          a1 += w * (mu * (b / s) * ((s + nt) / (s + 1.0)));
+        } else {
+          a2 += w * ((mu - e1) * (mu - e1));
+        }
+      }
+    }
+  }
+  mean = nt * a0;
+  var = nt * a1 + nt * nt * a2;
+}
+
+// ---- Binomial(n, p) variates.  Every loop is bounded at compile time.  The draw is made for q = min(p, 1 - p) and reflected.
+//   n q < 10    sequential inversion from 0 with P(0) = (1 - q)^n, P(j + 1) = P(j) (n - j) / (j + 1) q / (1 - q): at most 256 trips (the mass
+//               beyond them is below 1e-150 at a mean below 10); at exhaustion the trip count is the draw
+//   otherwise   Hoermann's BTRS transformed rejection (1993), at most 1000 trials, then floor(n q): the shape of the Poisson PTRS loop above
+__device__ inline double RowRng::binomial(double n, double p) {
+  if (!(p > 0.0)) return 0.0;
+  if (!(p < 1.0)) return n;
+  const bool flip = p > 0.5;
+  const double q = flip ? 1.0 - p : p;
+  double k = 0.0;
+  if (n * q < 10.0) {
+    const double r = q / (1.0 - q);
+    double pk = exp(n * log1p(-q)), u = uniform();
+    for (int it = 0; it < 256; ++it) {
+      if (u <= pk || k >= n) break;
+      u -= pk;
+      pk *= r * ((n - k) / (k + 1.0));
+      k += 1.0;
+    }
+  } else {
+    const double spq = sqrt(n * q * (1.0 - q)), b = 1.15 + 2.53 * spq, a = -0.0873 + 0.0248 * b + 0.01 * q, c = n * q + 0.5;
+    const double vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq, lr = log(q / (1.0 - q)), md = floor((n + 1.0) * q);
+    const double h = lgamma(md + 1.0) + lgamma(n - md + 1.0);
+    k = floor(n * q);
+    for (int it = 0; it < 1000; ++it) {
+      const double U = uniform() - 0.5, V = uniform(), us = 0.5 - fabs(U);
+      const double kk = floor((2.0 * a / us + b) * U + c);
+      if (kk < 0.0 || kk > n) continue;
+      if ((us >= 0.07 && V <= vr) || log(V * alpha / (a / (us * us) + b)) <= h - lgamma(kk + 1.0) - lgamma(n - kk + 1.0) + (kk - md) * lr) {
+        k = kk;
+        break;
+      }
+    }
+  }
+  return flip ? n - k : k;
 }

@@ -33,7 +33,7 @@ __device__ __forceinline__ void lpd_store(double mx, double s1, double s2, long 
 }
 
 // ---- rules of at most 20 nodes: one lane per row, the node loop in registers ---------------------------------------------------
-// y: [N], Ordinal [2][ldy] (lower, upper cut point); m, v: row n at m[n * ldf] (the task's column of a wider q(f) array)
+// y: [N], Ordinal [2][ldy] (lower, upper cut point), Binomial [3][ldy] (k, n, lc); m, v: row n at m[n * ldf] (the task's column of a wider q(f) array)
 template <int LIK>
 __global__ __launch_bounds__(256) void lpd_lane_kernel(double param, int T, long long N, const double* __restrict__ y, long long ldy,
                                                        const double* __restrict__ m, const double* __restrict__ v, int ldf, int absv,
@@ -62,7 +62,9 @@ __global__ __launch_bounds__(256) void lpd_lane_kernel(double param, int T, long
       lpd_add(mx, s1, s2, gh_wn(T, i), -0.5 * log(2.0 * M_PI) - 0.5 * log(var) - 0.5 * (d2 / var));
     }
   } else {
-    const double yaux = LIK == HMOGP_LIK_POISSON ? lgamma(yy + 1.0) : (LIK == HMOGP_LIK_ORDINAL ? y[ldy + n] : 0.0);
+    const double yaux = LIK == HMOGP_LIK_POISSON ? lgamma(yy + 1.0)
+                                                 : (LIK == HMOGP_LIK_ORDINAL ? y[ldy + n] : (lik_has_trials(LIK) ? y[2 * ldy + n] : 0.0));
+    if constexpr (lik_has_trials(LIK)) param = y[ldy + n];   // Binomial: y is [3][ldy] = (k, n, lc); the row's own n
     const double s = sqrt(2.0 * v0);
 #pragma unroll 1
     for (int i = 0; i < T; ++i) {
@@ -76,7 +78,7 @@ __global__ __launch_bounds__(256) void lpd_lane_kernel(double param, int T, long
 // ---- tensor rules: one wave per row, four rows per block ----------------------------------------------------------------------
 // JD = the family's functions (a template parameter: the node's f lives in registers under static indices only).  The node values of
 // dimension k go into the wave's own LDS slice at [20 k, 20 k + T), filled from global memory (a run-time k costs nothing there).
-// y: [N]; Weibull [2][ldy] (log y, delta); Dirichlet [K][ldy] (log y_k).
+// y: [N]; Weibull [2][ldy] (log y, delta); Dirichlet [K][ldy] (log y_k); Beta-Binomial [3][ldy] (k, n, lc).
 template <int LIK, int JD>
 __global__ __launch_bounds__(256) void lpd_wave_kernel(double param, int T, long long N, const double* __restrict__ y, long long ldy,
                                                        const double* __restrict__ m, const double* __restrict__ v, int ldf, int absv,
@@ -95,7 +97,9 @@ __global__ __launch_bounds__(256) void lpd_wave_kernel(double param, int T, long
   }
   __builtin_amdgcn_wave_barrier();  // written and read by this wave only
   const double yy = y[n];
-  const double yaux = LIK == HMOGP_LIK_NEGBINOMIAL ? lgamma(yy + 1.0) : (LIK == HMOGP_LIK_WEIBULL ? y[ldy + n] : 0.0);
+  const double yaux = LIK == HMOGP_LIK_NEGBINOMIAL ? lgamma(yy + 1.0)
+                                                   : (LIK == HMOGP_LIK_WEIBULL ? y[ldy + n] : (lik_has_trials(LIK) ? y[2 * ldy + n] : 0.0));
+  if constexpr (lik_has_trials(LIK)) param = y[ldy + n];   // Beta-Binomial: y is [3][ldy] = (k, n, lc); the row's own n
   double ly[LIK == HMOGP_LIK_DIRICHLET ? JD : 1];
   if (LIK == HMOGP_LIK_DIRICHLET) {
 #pragma unroll
@@ -158,12 +162,14 @@ void launch_log_predictive_gh(const LpdArgs& a, hipStream_t s) {
     case HMOGP_LIK_POISSON: LANE(HMOGP_LIK_POISSON); break;
     case HMOGP_LIK_EXPONENTIAL: LANE(HMOGP_LIK_EXPONENTIAL); break;
     case HMOGP_LIK_ORDINAL: LANE(HMOGP_LIK_ORDINAL); break;
+    case HMOGP_LIK_BINOMIAL: LANE(HMOGP_LIK_BINOMIAL); break;
     case HMOGP_LIK_HETGAUSSIAN: LANE(HMOGP_LIK_HETGAUSSIAN); break;
     case HMOGP_LIK_GAMMA: WAVE(HMOGP_LIK_GAMMA, 2); break;
     case HMOGP_LIK_BETA: WAVE(HMOGP_LIK_BETA, 2); break;
     case HMOGP_LIK_STUDENT: WAVE(HMOGP_LIK_STUDENT, 2); break;
     case HMOGP_LIK_NEGBINOMIAL: WAVE(HMOGP_LIK_NEGBINOMIAL, 2); break;
     case HMOGP_LIK_WEIBULL: WAVE(HMOGP_LIK_WEIBULL, 2); break;
+    case HMOGP_LIK_BETABINOMIAL: WAVE(HMOGP_LIK_BETABINOMIAL, 2); break;
     case HMOGP_LIK_CATEGORICAL:
       switch (a.J) {
         case 1: WAVE(HMOGP_LIK_CATEGORICAL, 1); break;

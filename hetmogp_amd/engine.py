@@ -14,7 +14,10 @@ from ._lib import lib, check
 LIK_IDS = dict(Gaussian=_lib.LIK_GAUSSIAN, Bernoulli=_lib.LIK_BERNOULLI, HetGaussian=_lib.LIK_HETGAUSSIAN,
                Categorical=_lib.LIK_CATEGORICAL, Poisson=_lib.LIK_POISSON, Exponential=_lib.LIK_EXPONENTIAL,
                Gamma=_lib.LIK_GAMMA, Beta=_lib.LIK_BETA, Student=_lib.LIK_STUDENT, Ordinal=_lib.LIK_ORDINAL,
-               Dirichlet=_lib.LIK_DIRICHLET, NegBinomial=_lib.LIK_NEGBINOMIAL, Weibull=_lib.LIK_WEIBULL)
+               Dirichlet=_lib.LIK_DIRICHLET, NegBinomial=_lib.LIK_NEGBINOMIAL, Weibull=_lib.LIK_WEIBULL,
+               Binomial=_lib.LIK_BINOMIAL, BetaBinomial=_lib.LIK_BETABINOMIAL)
+
+_TWO_COLUMN_Y = {"Weibull": "(time, event indicator)", "Binomial": "(successes k, trials n)", "BetaBinomial": "(successes k, trials n)"}
 
 
 def _f64(a):
@@ -32,21 +35,22 @@ def lik_dim_f(name, **kw):
     if name == "Dirichlet":
         return int(kw["K"])
     return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1,
-                NegBinomial=2, Weibull=2)[name]
+                NegBinomial=2, Weibull=2, Binomial=1, BetaBinomial=2)[name]
 
 
 def lik_dim_y(name, **kw):
-    """Columns of a task's Y (the reference's ``get_metadata()[0]``): 1, but K for a Dirichlet task and 2 (time, event
-    indicator) for a Weibull task."""
-    return int(kw["K"]) if name == "Dirichlet" else (2 if name == "Weibull" else 1)
+    """Columns of a task's Y (the reference's ``get_metadata()[0]``): 1, but K for a Dirichlet task and 2 for a Weibull (time, event
+    indicator), Binomial or BetaBinomial (successes, trials) task."""
+    return int(kw["K"]) if name == "Dirichlet" else (2 if name in _TWO_COLUMN_Y else 1)
 
 
 def _y_rows(name, y, **kw):
-    """y of one task as the library reads it: (N,), or (N, K) row-major for a Dirichlet task, (N, 2) for a Weibull task (whose second
-    column is a flag, not an observation: an array of any other shape is refused instead of being reshaped into pairs)."""
+    """y of one task as the library reads it: (N,), or (N, K) row-major for a Dirichlet task, (N, 2) for a Weibull, Binomial or
+    BetaBinomial task (whose second column is a flag or a trial count, not an observation: an array of any other shape is refused
+    instead of being reshaped into pairs)."""
     dy = lik_dim_y(name, **kw)
-    if name == "Weibull" and (np.ndim(y) != 2 or np.shape(y)[1] != 2):
-        raise _lib.InvalidArgument("Weibull: Y must be (N, 2) = (time, event indicator), got shape %r" % (np.shape(y),))
+    if name in _TWO_COLUMN_Y and (np.ndim(y) != 2 or np.shape(y)[1] != 2):
+        raise _lib.InvalidArgument("%s: Y must be (N, 2) = %s, got shape %r" % (name, _TWO_COLUMN_Y[name], np.shape(y)))
     return _f64(y).reshape(-1) if dy == 1 else _f64(y).reshape(-1, dy)
 
 
@@ -84,6 +88,8 @@ def lik_param(name, **kw):
         if "table_id" in kw:                           # an id from ordinal_table(), passed through as it is
             return float(kw["table_id"])
         return ordinal_table(kw.get("K"), kw.get("bin_edges"), kw.get("sigma", 1.0))
+    if name in ("Binomial", "BetaBinomial"):           # the trial count n* of predictive / sample; the library refuses a non-integer
+        return float(kw.get("pred_trials", 1))         # or one outside 1 .. 1e9 (0 means 1)
     return 0.0
 
 
@@ -658,7 +664,8 @@ PREDQ_FAMILIES = ("Gaussian", "HetGaussian", "Bernoulli", "Exponential", "Ordina
 PREDQ_MISSING = {"Poisson": "a regularised incomplete gamma function", "Gamma": "a regularised incomplete gamma function",
                  "Beta": "a regularised incomplete beta function", "Student": "a regularised incomplete beta function",
                  "NegBinomial": "a regularised incomplete beta function", "Categorical": "an order of its classes (it has none)",
-                 "Dirichlet": "a univariate outcome (it is multivariate)"}
+                 "Dirichlet": "a univariate outcome (it is multivariate)",
+                 "Binomial": "a regularised incomplete beta function", "BetaBinomial": "a regularised incomplete beta function"}
 
 
 def predq_require(name):
@@ -701,10 +708,10 @@ def predictive_quantile_rows(name, m, v, probs, gh_T=0, device=None, **kw):
 
 def sample(name, F, seed=0, device=None, **kw):
     """One draw y ~ p(y | F[n]) per row on the device (the reference's `<likelihood>.samples`): returns (N, 1); (N, K) for
-    Dirichlet.  Weibull: event times (N, 1), never censored."""
+    Dirichlet.  Weibull: event times (N, 1), never censored.  Binomial, BetaBinomial: counts (N, 1) out of pred_trials trials."""
     device = _resolve_device(device)
     J = lik_dim_f(name, **kw)
     F = _f64(F).reshape(-1, J)
-    Y = np.zeros((F.shape[0], 1 if name == "Weibull" else lik_dim_y(name, **kw)))
+    Y = np.zeros((F.shape[0], 1 if name in _TWO_COLUMN_Y else lik_dim_y(name, **kw)))
     check(lib.hmogp_sample(device, LIK_IDS[name], lik_param(name, **kw), F.shape[0], int(seed) & (2 ** 64 - 1), _p(F), _p(Y)))
     return Y

@@ -18,6 +18,9 @@ LPD_ESS_WARN = {
     "Gaussian": 0.0, "Bernoulli": 2.4, "Poisson": 2.0, "Exponential": 2.3, "Ordinal": 2.4, "HetGaussian": 2.4,      # Bernoulli *, Ordinal *
     "Gamma": 11.2, "Beta": 9.0, "Student": 13.8, "Weibull": 14.2, "NegBinomial": 14.2,                              # NegBinomial *
     "Dirichlet": 28.3, "Categorical": 0.0,
+    # (rows (k, n) with n log-uniform in 1 .. 2000: tests/test_binom_cpu.py::test_lpd_ess_warn_is_measured re-measures these two.  A row of
+    #  many trials is a narrow likelihood: 23 of the 232 Binomial rows whose dense integral settles miss 1e-2, ten of them at v <= 0.25)
+    "Binomial": 2.1, "BetaBinomial": 6.0,
 }
 
 
@@ -371,6 +374,32 @@ class Weibull(_Lik):
 
     def __init__(self, gp_link=None):
         pass
+
+
+class Binomial(_Lik):
+    """Binomial likelihood with per-row trial counts (not in the reference; the model is DESIGN 9l): k successes out of n trials with
+    p = clip(e^f / (1 + e^f), 1e-9, 1 - 1e-9), Bernoulli's link and clip, so that a row (k, n) is exactly n Bernoulli rows collapsed into
+    one.  Y is (N, 2): (k, n), integers with 1 <= n <= 1e9 and 0 <= k <= n; anything else is refused by the library.  `predictive` and
+    `samples` receive no y: they describe a count out of `pred_trials` trials (an integer in 1 .. 1e9).  `log_predictive` and
+    `log_predictive_density` take (N, 2) test rows.  There is no parameter to learn, and the predictive cdf / quantiles are not built.
+    The link is fixed (`gp_link` is accepted for the reference's signature and not used)."""
+    name = "Binomial"
+    _dims = (2, 1, 1)
+
+    def __init__(self, gp_link=None, pred_trials=1):
+        self.pred_trials = pred_trials
+
+    def kwargs(self):
+        return dict(pred_trials=self.pred_trials)
+
+
+class BetaBinomial(Binomial):
+    """Beta-Binomial likelihood, Binomial's over-dispersed sibling: k successes out of n trials whose success probability is
+    itself Beta(a, b), a = clip(exp(f0), 1e-9, 1e9), b = clip(exp(f1), 1e-9, 1e9) (Beta's links and clips).  Mean n a / (a + b), variance
+    n mu (1 - mu) (a + b + n) / (a + b + 1): a + b -> inf is the Binomial.  Y, `pred_trials`, `predictive`, `samples` and the log
+    predictive routines as Binomial's."""
+    name = "BetaBinomial"
+    _dims = (2, 2, 1)
 
 
 class Categorical(_Lik):

@@ -5,7 +5,7 @@ conditioned at large M.  Used by bench.py, smoke() and the size-p
 import numpy as np
 
 _DIM_F = dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1,
-              NegBinomial=2, Weibull=2)
+              NegBinomial=2, Weibull=2, Binomial=1, BetaBinomial=2)
 
 
 def _dim_f(name, kw):
@@ -49,6 +49,9 @@ def _sample(rng, name, kw, F):
         return rng.poisson(np.exp(np.clip(F[:, :1], -5, 3)) * rng.gamma(r) / r).astype(float)
     if name == "Weibull":                      # (time, event indicator): censored at an independent Weibull censoring time
         return weibull_censored(rng, np.clip(F[:, :1], -3, 3), np.clip(F[:, 1:2], -1, 1.5), kw.get("censored", 0.3))
+    if name in ("Binomial", "BetaBinomial"):   # (successes, trials): the trials drawn per row from kw["trials"] = (lo, hi), inclusive
+        lo, hi = kw.get("trials", (1, 30))
+        return binomial_counts(rng, name, F, lo, hi)
     if name == "Ordinal":                      # labels 1..K drawn from the model; F spread so that every class occurs
         from .engine import ordinal_edges
         edges = ordinal_edges(kw.get("K"), kw.get("bin_edges"))
@@ -82,6 +85,22 @@ def weibull_censored(rng, f0, f1, censored=0.3):
         return np.hstack([t, np.ones_like(t)])
     c = np.exp(f0) * ((1.0 - censored) / censored * u) ** ik          # s^k = (1 - censored) / censored
     return np.hstack([np.minimum(t, c), (t <= c).astype(float)])
+
+
+def binomial_counts(rng, name, F, lo=1, hi=30):
+    """(N, 2) rows (k, n) of a Binomial or BetaBinomial task: the trial count n of each row is drawn uniformly from the integers
+    lo .. hi (1 <= lo <= hi <= 1e9), k from the row's own law -- Binomial(n, sigmoid(f0)), or Binomial(n, p) with
+    p ~ Beta(exp f0, exp f1) (f clipped to [-2, 3] so that the draws stay off the ends)."""
+    lo, hi = int(lo), int(hi)
+    if not 1 <= lo <= hi <= 10 ** 9:
+        raise ValueError("trials must satisfy 1 <= lo <= hi <= 1e9, got %r" % ((lo, hi),))
+    F = np.asarray(F, float)
+    n = rng.randint(lo, hi + 1, (F.shape[0], 1))
+    if name == "Binomial":
+        p = 1.0 / (1.0 + np.exp(-F[:, :1]))
+    else:
+        p = rng.beta(np.exp(np.clip(F[:, :1], -2, 3)), np.exp(np.clip(F[:, 1:2], -2, 3)))
+    return np.hstack([rng.binomial(n, p).astype(float), n.astype(float)])
 
 
 def make_case(specs, Ns, M, Q, P=1, seed=0, c=(0.8, 1.0, 1.3, 1.1, 0.9, 1.2, 1.0, 0.85)):

@@ -47,8 +47,25 @@ enum {
   HMOGP_LIK_ORDINAL = 9,     /* ordinal.py      param = id from hmogp_ordinal_table   dim_f = 1   */
   HMOGP_LIK_DIRICHLET = 10,  /* dirichlet.py    param = K (2 .. HMOGP_DIRICHLET_MAXK)  dim_f = K, Y is [N, K] */
   HMOGP_LIK_NEGBINOMIAL = 11, /* (not in the reference)  no param (0.0 is passed and ignored)  dim_f = 2 */
-  HMOGP_LIK_WEIBULL = 12      /* (not in the reference)  no param (0.0 is passed and ignored)  dim_f = 2, Y is [N, 2] */
+  HMOGP_LIK_WEIBULL = 12,     /* (not in the reference)  no param (0.0 is passed and ignored)  dim_f = 2, Y is [N, 2] */
+  HMOGP_LIK_BINOMIAL = 13,    /* (not in the reference)  param = trial count n* of predictive / sample (0.0: 1)  dim_f = 1, Y is [N, 2] */
+  HMOGP_LIK_BETABINOMIAL = 14 /* (not in the reference)  param as Binomial's                                    dim_f = 2, Y is [N, 2] */
 };
+
+/* Binomial and Beta-Binomial: k successes out of n trials, n the row's own.  Y is [N, 2] row-major: (k, n), both finite,
+ * integer-valued doubles with 1 <= n <= 1e9 and 0 <= k <= n.  With lc = lgamma(n+1) - lgamma(k+1) - lgamma(n-k+1):
+ *   Binomial      one function, Bernoulli's link and clip p = clip(e^f / (1 + e^f), 1e-9, 1 - 1e-9):
+ *                   log p(k | n, f) = lc + k log p + (n - k) log(1 - p)            (a row (k, n) is n Bernoulli rows collapsed into one)
+ *   BetaBinomial  two functions, Beta's links and clips a = clip(exp(f0), 1e-9, 1e9), b = clip(exp(f1), 1e-9, 1e9), s = a + b:
+ *                   log p(k | n, f) = lc + G(k, a) + G(n - k, b) - G(n, s),        G(y, r) = lgamma(y + r) - lgamma(r)
+ *                 the over-dispersed sibling: mean n a / s, variance n (a / s) (b / s) (s + n) / (s + 1).
+ * Anything else in Y is HMOGP_E_INVALID (the family's name in the message) in hmogp_set_task_data (the task keeps its previous data) and
+ * in every building block that takes y (hmogp_var_exp[_ex], hmogp_log_predictive, hmogp_log_predictive_gh, whose y is [N, 2] as well).
+ * lik_param is the trial count n* of hmogp_predictive and hmogp_sample, which receive no y: an integer-valued double in 1 .. 1e9, 0.0
+ * meaning 1; anything else is HMOGP_E_INVALID in hmogp_create and in every building block.  It is ignored wherever y carries n.
+ * hmogp_sample writes counts [N, 1]; hmogp_predictive the mean and variance of a count out of n* trials.  Neither family has a parameter
+ * of its own: hmogp_lik_param_count answers 0 and hmogp_var_exp_dparam refuses them.  The predictive cdf and quantiles are refused (they
+ * need the regularised incomplete beta function).  New enum values only: ABI version 8 stays. */
 
 /* Weibull with right-censoring: times to an event that may be only partly observed.  f0 = log of the scale lambda,
  * f1 = log of the shape k = clip(exp(f1), 1e-3, 1e3).  Y is [N, 2] row-major: (y, delta), y finite and > 0, delta exactly 1.0 (the

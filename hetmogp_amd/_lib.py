@@ -22,8 +22,10 @@ LIK_NEGBINOMIAL = 11     # heteroscedastic Negative Binomial for over-dispersed 
 LIK_WEIBULL = 12         # Weibull with right-censoring (not in the reference); no lik_param, Y is (N, 2) = (time, event indicator)
 LIK_BINOMIAL = 13        # k successes out of n trials, n per row (not in the reference); lik_param = trial count n* of predictive / sample, Y is (N, 2) = (k, n)
 LIK_BETABINOMIAL = 14    # its over-dispersed sibling, two latent functions; lik_param and Y as Binomial's
+LIK_ZIPOISSON = 15       # zero-inflated Poisson: f0 = log rate, f1 = logit of the structural-zero probability (not in the reference); no lik_param
 LIK_IDS_BY_NAME = dict(Gaussian=0, Bernoulli=1, HetGaussian=2, Categorical=3, Poisson=4, Exponential=5, Gamma=6, Beta=7,
-                       Student=8, Ordinal=9, Dirichlet=10, NegBinomial=11, Weibull=12, Binomial=13, BetaBinomial=14)
+                       Student=8, Ordinal=9, Dirichlet=10, NegBinomial=11, Weibull=12, Binomial=13, BetaBinomial=14,
+                       ZIPoisson=15)
 QUANT_MAXP = 8          # most probabilities per hmogp_predictive_quantile / hmogp_predict_quantile call
 E_INVALID, E_NO_DEVICE, E_NOT_PD, E_SQI_UNSTABLE, E_STATE, E_COMM = -1, -2, -3, -4, -5, -6
 NTIMINGS = 11

@@ -46,12 +46,18 @@ void check_trials_first(int lik_id, double lik_param) {
   if (lik_id == HMOGP_LIK_BINOMIAL || lik_id == HMOGP_LIK_BETABINOMIAL) check_lik_param(lik_id, lik_param);
 }
 
+// Zero-inflated Poisson: the counts are refused on the host, before the device is asked for (the same answer with or without one)
+void check_counts_first(int lik_id, int64_t N, const double* y) {
+  if (lik_id == HMOGP_LIK_ZIPOISSON && y && N > 0) zipoisson_check_rows(y, N);
+}
+
 }  // namespace
 
 namespace hmogp_detail {
 // y [N] of a building block -> device.  Ordinal: the labels are checked and replaced by the rows' lower, then upper cut points
 // ([2][N], what launch_var_exp / launch_log_predictive read), so that the device code is the engine's.  Dirichlet: y is [N][K]; it is
-// checked and replaced by log y_k as [K][N], the engine's layout.  Negative Binomial: the counts are checked and uploaded as they are.
+// checked and replaced by log y_k as [K][N], the engine's layout.  Negative Binomial, zero-inflated Poisson: the counts are checked and
+// uploaded as they are.
 // Weibull: y is [N][2] = (y, delta); it is checked and replaced by (log y, delta) as [2][N], the engine's layout.
 // Binomial, Beta-Binomial: y is [N][2] = (k, n); it is checked and replaced by (k, n, lc) as [3][N].
 // `tb`: the Ordinal table to cut by instead of the registry entry `lik_param` names (a task's private table).
@@ -79,6 +85,7 @@ void upload_y_image(int lik_id, double lik_param, const OrdinalTable* tb, const 
     return;
   }
   if (lik_id == HMOGP_LIK_NEGBINOMIAL) negbinomial_check_rows(y, N);
+  if (lik_id == HMOGP_LIK_ZIPOISSON) zipoisson_check_rows(y, N);
   if (lik_id != HMOGP_LIK_ORDINAL) {
     dy.ensure(sizeof(double) * N);
     HIP_TRY(hipMemcpy(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice));
@@ -484,6 +491,7 @@ int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t 
                      const double* m, const double* v, double* ve, double* dm, double* dv) {
   return guarded(nullptr, [&] {
     check_trials_first(lik_id, lik_param);
+    check_counts_first(lik_id, N, y);
     need_device(device);
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);
@@ -578,6 +586,7 @@ int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64
                          const double* y, const double* m, const double* v, double* log_pred) {
   return guarded(nullptr, [&] {
     check_trials_first(lik_id, lik_param);
+    check_counts_first(lik_id, N, y);
     need_device(device);
     const int J = lik_dimf(lik_id, lik_param);
     check_lik_param(lik_id, lik_param);
@@ -610,6 +619,7 @@ int hmogp_log_predictive_gh(int32_t device, int32_t lik_id, double lik_param, in
                             const double* m, const double* v, double* lpd, double* ess) {
   return guarded(nullptr, [&] {
     check_trials_first(lik_id, lik_param);
+    check_counts_first(lik_id, N, y);
     need_device(device);
     if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
     const int J = lik_dimf(lik_id, lik_param);

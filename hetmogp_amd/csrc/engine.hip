@@ -180,6 +180,7 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
     dirichlet_log_rows(k.dimf, Y, N, cuts.data());
   }
   if (k.lik == HMOGP_LIK_NEGBINOMIAL && N > 0) negbinomial_check_rows(Y, N);   // counts, checked before the task's state changes
+  if (k.lik == HMOGP_LIK_ZIPOISSON && N > 0) zipoisson_check_rows(Y, N);
   if (k.lik == HMOGP_LIK_WEIBULL && N > 0) {   // Y is [N, 2] = (y, delta); checked, and (log y, delta) laid out [2][N], before the state changes
     cuts.resize(2 * (size_t)N);
     weibull_check_rows(Y, N, cuts.data());
@@ -197,7 +198,7 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
   k.Y.ensure(sizeof(double) * N * k.dimy());
   HIP_TRY(hipMemcpy(k.X.p, X, sizeof(double) * N * P, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(k.Y.p, Y, sizeof(double) * N * k.dimy(), hipMemcpyHostToDevice));
-  if (k.lik == HMOGP_LIK_POISSON || k.lik == HMOGP_LIK_NEGBINOMIAL) {  // gammaln(y+1) depends on the data only (poisson.py:33)
+  if (k.lik == HMOGP_LIK_POISSON || k.lik == HMOGP_LIK_NEGBINOMIAL || k.lik == HMOGP_LIK_ZIPOISSON) {  // gammaln(y+1) depends on the data only (poisson.py:33)
     k.Yaux.ensure(sizeof(double) * N);
     launch_gammaln1p(k.Y.d(), k.Yaux.d(), N, st);
     HIP_TRY(hipStreamSynchronize(st));

@@ -144,6 +144,7 @@ void check_lik_param(int lik, double param);  // HMOGP_E_INVALID for a parameter
 // Dirichlet: compositions y [N][K] (every y_k finite and > 0, |sum_k y_k - 1| <= 1e-6, else HMOGP_E_INVALID) -> ly [K][N] = log y_k
 void dirichlet_log_rows(int K, const double* y, long long N, double* ly);
 void negbinomial_check_rows(const double* y, long long N);   // HMOGP_E_INVALID unless every y is a finite, non-negative integer
+void zipoisson_check_rows(const double* y, long long N);     // the same check for the zero-inflated Poisson, under its own name
 // Weibull: rows (y, delta) [N][2] (y finite and > 0, delta exactly 0 or 1, else HMOGP_E_INVALID) -> img [2][N] = log y, delta
 void weibull_check_rows(const double* y, long long N, double* img);
 // Binomial / Beta-Binomial: rows (k, n) [N][2] (integers, 1 <= n <= 1e9, 0 <= k <= n, else HMOGP_E_INVALID with the family's name) ->

@@ -22,7 +22,8 @@ int lik_dimf(int lik, double param) {
     case HMOGP_LIK_STUDENT:
     case HMOGP_LIK_NEGBINOMIAL:
     case HMOGP_LIK_WEIBULL:
-    case HMOGP_LIK_BETABINOMIAL: return 2;
+    case HMOGP_LIK_BETABINOMIAL:
+    case HMOGP_LIK_ZIPOISSON: return 2;
     case HMOGP_LIK_CATEGORICAL: return (int)param - 1;
     case HMOGP_LIK_DIRICHLET: return (param >= 2.0 && param <= (double)HMOGP_DIRICHLET_MAXK) ? (int)param : -1;
     default: return -1;
@@ -57,6 +58,13 @@ void binomial_check_rows(int lik, const double* y, long long N, double* img) {
     img[N + i] = n;
     img[2 * N + i] = std::lgamma(n + 1.0) - std::lgamma(k + 1.0) - std::lgamma(n - k + 1.0);
   }
+}
+
+// ------------------------------------------------------------------------------------ zero-inflated Poisson rows
+void zipoisson_check_rows(const double* y, long long N) {
+  for (long long n = 0; n < N; ++n)
+    if (!(std::isfinite(y[n]) && y[n] >= 0.0 && y[n] == std::floor(y[n])))
+      throw EngineError{HMOGP_E_INVALID, "ZIPoisson: every y must be a finite, non-negative integer"};
 }
 
 // ------------------------------------------------------------------------------------ Negative Binomial rows

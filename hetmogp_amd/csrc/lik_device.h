@@ -8,7 +8,8 @@
 //   Q2  Categorical: d/dm is the constant onehot(y)[d] - 1 (categorical.py:102-113)
 // At the end of the file: the derivatives with respect to the likelihoods' OWN parameters (Gaussian sigma, Student nu, Ordinal cut
 // points and sigma), appended so that nothing above them changes; and, appended last, the Binomial and Beta-Binomial families
-// with per-row trial counts (one lane per row and one wave per row).
+// with per-row trial counts (one lane per row and one wave per row), and after them the zero-inflated Poisson (one
+// wave per row: 40 nodes where y >= 1, 400 where y = 0).
 // Lane mapping: closed forms, 1-D quadratures and Gamma (separable in its two functions) use ONE lane per row;
 // Beta (100 nodes), Student, Negative Binomial and Weibull (400 nodes), Categorical (10^(K-1) nodes) and Dirichlet (10^K nodes) use ONE WAVE per row,
 // nodes strided over the 64 lanes and reduced with wavefront shuffles.
@@ -38,6 +39,11 @@ __device__ __forceinline__ double lik_betabinomial_logpdf(double k, double n, do
 __device__ __forceinline__ void lik_binomial_predictive(double m, double v, double param, int T, double& mean, double& var);
 __device__ __forceinline__ void lik_betabinomial_predictive(const double* m, const double* v, double param, int T, double& mean,
                                                             double& var);
+
+// Zero-inflated Poisson: defined after them, at the end of this file
+__device__ __forceinline__ void lik_zipoisson_wave(double y, double lgy1, const double* m, const double* v, int lane, double* tab, LikOut& o);
+__device__ __forceinline__ double lik_zipoisson_logpdf(double y, double lgy1, const double* f);
+__device__ __forceinline__ void lik_zipoisson_predictive(const double* m, const double* v, int T, double& mean, double& var);
 
 __device__ __forceinline__ double safe_exp(double f) { return exp(fmin(f, LIM_VAL)); }
 __device__ __forceinline__ double safe_square(double f) {
@@ -241,7 +247,8 @@ __device__ __forceinline__ void lik_ordinal_predictive(const OrdinalTable& tb, d
 // [56,64) m_k, v_k (predictive, T = 20: [0,80) a_k(node i), [80,88) m_k, v_k); Negative Binomial [0,20) min(f0(node i), LIM_VAL), then
 // per node j of f1: [20,40) log r_j, [40,60) r_j, [60,80) G_j - lgamma(y+1), [80,100) r_j D1_j, [100,120) r_j^2 D2_j;
 // Weibull [0,20) log y - f0(node i), [20,40) k_j, [40,60) log k_j; Beta-Binomial [0,80) a_i, G(k, a_i), a_i D1(k, a_i), a_i^2 D2(k, a_i),
-// [80,160) the same four for b_j with n - k.
+// [80,160) the same four for b_j with n - k; zero-inflated Poisson (rows with y = 0 only) [0,20) lambda_i, [20,40) -expm1(-lambda_i), then per
+// node j of f1: [40,60) log pi_j, [60,80) log(1 - pi_j), [80,100) pi_j, [100,120) pi_j (1 - pi_j).
 #define HMOGP_ETAB 176
 
 __device__ __forceinline__ double wave_min(double v) {
@@ -995,6 +1002,8 @@ __device__ __forceinline__ void lik_predictive(const double* m, const double* v,
     lik_binomial_predictive(m[0], v[0], param, T, mean[0], var[0]);
   } else if (LIK == HMOGP_LIK_BETABINOMIAL) {
     lik_betabinomial_predictive(m, v, param, T, mean[0], var[0]);
+  } else if (LIK == HMOGP_LIK_ZIPOISSON) {  // one lane per row, the T nodes over f1
+    lik_zipoisson_predictive(m, v, T, mean[0], var[0]);
   } else {  // Categorical, categorical.py:84-99,224-269: E[rho_d], rho normalised over the K-1 columns; variance zeros
     const int D = (int)param - 1;
     for (int e = lane; e < D * 10; e += 64) {
@@ -1162,6 +1171,8 @@ __device__ __forceinline__ double lik_logpdf_sample(double y, double yaux, const
     return lik_binomial_logpdf(y, param, yaux, f);
   } else if (LIK == HMOGP_LIK_BETABINOMIAL) {
     return lik_betabinomial_logpdf(y, param, yaux, f);
+  } else if (LIK == HMOGP_LIK_ZIPOISSON) {  // yaux = lgamma(y + 1)
+    return lik_zipoisson_logpdf(y, yaux, f);
   }
   return nan("");
 }
@@ -1279,6 +1290,9 @@ __device__ __forceinline__ double lik_sample(RowRng& g, const double* f, double 
     // (both variates underflow where a and b are tiny: the mass sits on p = 0 and p = 1, p = 1 with probability a / (a + b))
     const double p = x + yv > 0.0 ? x / (x + yv) : (g.uniform() * (a + b) < a ? 1.0 : 0.0);
     return g.binomial(param > 0.0 ? param : 1.0, p);
+  } else if (LIK == HMOGP_LIK_ZIPOISSON) {  // a structural zero with probability pi, else a Poisson count
+    const double ef = safe_exp(f[1]);
+    return g.uniform() < clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9) ? 0.0 : g.poisson(safe_exp(f[0]));
   } else {  // Categorical: labels 1..K, probabilities clipped then renormalised (categorical.py:66-71)
     const int K = (int)param, D = K - 1;
     double e[HMOGP_MAXJ], esum = 0.0;
@@ -1353,7 +1367,7 @@ __host__ __device__ constexpr int lik_pred_lanes(int lik) {
 // lanes per row of a likelihood
 __host__ __device__ constexpr int lik_lanes(int lik) {
   return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_STUDENT || lik == HMOGP_LIK_DIRICHLET ||
-          lik == HMOGP_LIK_NEGBINOMIAL || lik == HMOGP_LIK_WEIBULL || lik == HMOGP_LIK_BETABINOMIAL)
+          lik == HMOGP_LIK_NEGBINOMIAL || lik == HMOGP_LIK_WEIBULL || lik == HMOGP_LIK_BETABINOMIAL || lik == HMOGP_LIK_ZIPOISSON)
              ? 64
              : 1;
 }
@@ -1387,6 +1401,8 @@ __device__ __forceinline__ void lik_eval(double y, double yaux, const double* m,
     lik_binomial_quad(y, param, yaux, m[0], v[0], o);   // y: k, param: the row's own trial count n, yaux: lc
   else if (LIK == HMOGP_LIK_BETABINOMIAL)
     lik_betabinomial_wave(y, param, yaux, m, v, lane, etab, o);
+  else if (LIK == HMOGP_LIK_ZIPOISSON)
+    lik_zipoisson_wave(y, yaux, m, v, lane, etab, o);   // yaux: lgamma(y + 1)
   else
     lik_categorical_t<(CATD > 0 ? CATD : 1)>(y, m, v, lane, etab, quirks, o);
   if ((LIK == HMOGP_LIK_GAMMA || LIK == HMOGP_LIK_BETA) && !(quirks & HMOGP_QUIRK_GAMMA_BETA_PI)) {
@@ -1733,4 +1749,98 @@ __device__ inline double RowRng::binomial(double n, double p) {
     }
   }
   return flip ? n - k : k;
+}
+
+// ============================================================================ Zero-inflated Poisson
+// Counts with more zeros than a rate explains: a structural zero with probability pi, else Poisson(lambda).  f0 = log of the rate,
+// lambda = safe_exp(f0) (Poisson's link); f1 = logit of pi = clip(e^f1 / (1 + e^f1), 1e-9, 1 - 1e-9) (Bernoulli's link and clip, in Bernoulli's
+// expression shapes).  The clip's own derivative is ignored, as for every clipped family.  Appended so that nothing in front changes.
+//   y >= 1   log p = [-lambda + y f0 - lgamma(y+1)] + log(1 - pi): Poisson's log p in f0 plus Bernoulli's log p of the label 0 in f1.  The row
+//            is the SUM of two 20-node rules (the weights sum to 1 per dimension): 40 nodes, not 400.
+//   y  = 0   log p0 = lpi + softplus(u),  lpi = log pi, l1 = log(1 - pi), u = l1 - lambda - lpi,  rho = sigmoid(u) the Poisson component's
+//            share of the zero (rho and 1 - rho from the one exp(-|u|)), t = lambda rho, g = pi (1 - pi) (-expm1(-lambda)) exp(-log p0):
+//              d/df0 = -t     d2/df0^2 = -t + (lambda t) (1 - rho)     d/df1 = g     d2/df1^2 = g (rho - pi)
+//            In this order no product is inf * 0: once lambda is so large that rho is exactly 0, t is exactly 0 although lambda^2 would
+//            overflow.  g is a product of positive factors, never the difference (1 - rho) - pi, which cancels to nothing for small lambda.
+// y is the same in the whole wave (one wave per row): the branch on y = 0 does not diverge.
+__device__ __forceinline__ double lik_zipoisson_logpdf(double y, double lgy1, const double* f) {
+  const double lam = safe_exp(f[0]), ef = safe_exp(f[1]);
+  const double p = clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9);
+  if (y > 0.0) return (-lam + y * f[0] - lgy1) + log(1.0 - p);
+  const double lpi = log(p), u = log(1.0 - p) - lam - lpi;
+  return lpi + (fmax(u, 0.0) + log1p(exp(-fabs(u))));
+}
+
+__device__ __forceinline__ void lik_zipoisson_wave(double y, double lgy1, const double* m, const double* v, int lane, double* tab, LikOut& o) {
+  static_assert(120 <= HMOGP_ETAB, "zero-inflated Poisson table");
+  const bool on = lane < 40;   // lanes 0-19: node i of f0, lanes 20-39: node j of f1, lanes 40-63: idle here (index 0, weight 0)
+  const int dim = lane >= 20 ? 1 : 0, i = on ? lane - 20 * dim : 0;
+  const double f = on ? GH20_X[i] * sqrt(2.0 * (dim == 0 ? v[0] : v[1])) + (dim == 0 ? m[0] : m[1]) : 0.0;
+  const double ef = safe_exp(f);
+  if (y > 0.0) {
+    // lanes 0-19: lik_quad1d<POISSON>'s node i; lanes 20-39: lik_quad1d<BERNOULLI>'s node j at the label 0, both in their expression shapes
+    const double w = on ? GH20_WN[i] : 0.0;
+    const double p = clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9);
+    const double lp = dim == 0 ? -ef + y * f - lgy1 : log(1.0 - p);
+    const double d1 = dim == 0 ? -ef + y : ((0.0 - p) / (1.0 - p)) * (1.0 / (1.0 + ef));
+    const double d2 = dim == 0 ? -ef : -p / (1.0 + ef);
+    const double w0 = dim == 0 ? w : 0.0, w1 = dim == 0 ? 0.0 : w;
+    o.ve = wave_sum(lp * w0) + wave_sum(lp * w1);
+    o.gm[0] = wave_sum(d1 * w0);
+    o.gv[0] = 0.5 * wave_sum(d2 * w0);
+    o.gm[1] = wave_sum(d1 * w1);
+    o.gv[1] = 0.5 * wave_sum(d2 * w1);
+    return;
+  }
+  if (on) {
+    if (dim == 0) {
+      tab[i] = ef;
+      tab[20 + i] = -expm1(-ef);
+    } else {
+      const double p = clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9);
+      tab[40 + i] = log(p);
+      tab[60 + i] = log(1.0 - p);
+      tab[80 + i] = p;
+      tab[100 + i] = p * (1.0 - p);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();  // written and read by this wave only (LDS operations of a wave are in order)
+  double ve = 0.0, g0 = 0.0, g1 = 0.0, h0 = 0.0, h1 = 0.0;
+  for (int n = lane; n < 400; n += 64) {
+    const int a = n / 20, b = n - 20 * a;
+    const double w = GH20_WN[a] * GH20_WN[b];
+    const double lam = tab[a], lpi = tab[40 + b], pi = tab[80 + b];
+    const double u = tab[60 + b] - lam - lpi;
+    const double e = exp(-fabs(u)), inv = 1.0 / (1.0 + e), ei = e * inv;
+    const double lp0 = lpi + (fmax(u, 0.0) + log1p(e));
+    const double rho = u >= 0.0 ? inv : ei, rhoc = u >= 0.0 ? ei : inv;
+    const double t = lam * rho;
+    const double g = tab[100 + b] * tab[20 + a] * exp(-lp0);
+    ve += w * lp0;
+    g0 -= w * t;
+    h0 += w * (-t + (lam * t) * rhoc);
+    g1 += w * g;
+    h1 += w * (g * (rho - pi));
+  }
+  o.ve = wave_sum(ve);
+  o.gm[0] = wave_sum(g0);
+  o.gm[1] = wave_sum(g1);
+  o.gv[0] = 0.5 * wave_sum(h0);
+  o.gv[1] = 0.5 * wave_sum(h1);
+}
+
+// With q(f0), q(f1) independent and pbar = E[pi] over the T nodes of f1 (pi's clip kept, every other clip ignored, overflow is +inf):
+//   mean = (1 - pbar) exp(m0 + v0/2),   variance = (1 - pbar) (exp(m0 + v0/2) + exp(2 m0 + 2 v0)) - mean^2
+// (E[y | f] = (1 - pi) lambda, E[y^2 | f] = (1 - pi) (lambda + lambda^2)).  One lane per row.
+__device__ __forceinline__ void lik_zipoisson_predictive(const double* m, const double* v, int T, double& mean, double& var) {
+  const double s = sqrt(2.0 * v[1]);
+  double pb = 0.0;
+  for (int j = 0; j < T; ++j) {
+    const double ef = safe_exp(gh_x(T, j) * s + m[1]);
+    pb += clip(ef / (1.0 + ef), 1e-9, 1.0 - 1e-9) * gh_wn(T, j);
+  }
+  const double e1 = exp(m[0] + 0.5 * v[0]), e2 = exp(2.0 * m[0] + 2.0 * v[0]);
+  const double e2nd = (1.0 - pb) * (e1 + e2);
+  mean = (1.0 - pb) * e1;
+  var = e2nd < INFINITY ? e2nd - mean * mean : INFINITY;   // (mean^2 <= e2: finite wherever e2nd is)
 }

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void lpd_wave_kernel(double param, int T, long
   }
   __builtin_amdgcn_wave_barrier();  // written and read by this wave only
   const double yy = y[n];
-  const double yaux = LIK == HMOGP_LIK_NEGBINOMIAL ? lgamma(yy + 1.0)
+  const double yaux = (LIK == HMOGP_LIK_NEGBINOMIAL || LIK == HMOGP_LIK_ZIPOISSON) ? lgamma(yy + 1.0)
                                                    : (LIK == HMOGP_LIK_WEIBULL ? y[ldy + n] : (lik_has_trials(LIK) ? y[2 * ldy + n] : 0.0));
   if constexpr (lik_has_trials(LIK)) param = y[ldy + n];   // Beta-Binomial: y is [3][ldy] = (k, n, lc); the row's own n
   double ly[LIK == HMOGP_LIK_DIRICHLET ? JD : 1];
@@ -170,6 +170,7 @@ void launch_log_predictive_gh(const LpdArgs& a, hipStream_t s) {
     case HMOGP_LIK_NEGBINOMIAL: WAVE(HMOGP_LIK_NEGBINOMIAL, 2); break;
     case HMOGP_LIK_WEIBULL: WAVE(HMOGP_LIK_WEIBULL, 2); break;
     case HMOGP_LIK_BETABINOMIAL: WAVE(HMOGP_LIK_BETABINOMIAL, 2); break;
+    case HMOGP_LIK_ZIPOISSON: WAVE(HMOGP_LIK_ZIPOISSON, 2); break;
     case HMOGP_LIK_CATEGORICAL:
       switch (a.J) {
         case 1: WAVE(HMOGP_LIK_CATEGORICAL, 1); break;

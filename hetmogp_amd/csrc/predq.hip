@@ -373,6 +373,7 @@ const char* predq_refusal(int lik) {
     case HMOGP_LIK_BINOMIAL: return "predictive cdf / quantile: Binomial needs a regularised incomplete beta function, which is not built";
     case HMOGP_LIK_BETABINOMIAL:
       return "predictive cdf / quantile: BetaBinomial needs a regularised incomplete beta function, which is not built";
+    case HMOGP_LIK_ZIPOISSON: return "predictive cdf / quantile: ZIPoisson needs a regularised incomplete gamma function, which is not built";
     case HMOGP_LIK_CATEGORICAL: return "predictive cdf / quantile: Categorical has no order";
     case HMOGP_LIK_DIRICHLET: return "predictive cdf / quantile: Dirichlet is multivariate";
     default: return "predictive cdf / quantile: unknown likelihood id";

@@ -15,7 +15,7 @@ struct QuadArgs {
   long long N = 0;                 // rows of this chunk
   long long off = 0;               // added to the row index of the [Q][ldn] vectors below (0: the pointers are already offset)
   const double* y = nullptr;       // [N]
-  const double* yaux = nullptr;    // [N] gammaln(y+1) (Poisson, Negative Binomial) or nullptr
+  const double* yaux = nullptr;    // [N] gammaln(y+1) (Poisson, Negative Binomial, zero-inflated Poisson) or nullptr
   // Ordinal: y / yaux are the row's own LOWER / UPPER cut point (-inf / +inf at the ends) and lik_param is sigma
   const double* p = nullptr;       // [Q][ldn]  K^ a
   const double* c = nullptr;       // [Q][ldn]  rowsum(P~ .* K^)

@@ -411,7 +411,8 @@ __global__ __launch_bounds__(256) void quad_kernel(QuadArgs a) {
 // Student (id 8) takes bit 17, above Categorical's 8 + d (d <= 8), and Ordinal (id 9) bit 18, so that no bit of an existing family moves.
 // Dirichlet (id 10) takes bit 19 + (K - 2), K = 2 .. 4: one bit per K, like Categorical, so that each K is an instantiation of its own.
 // Negative Binomial (id 11) takes bit 22 (bit 11 is Categorical with three functions), Weibull (id 12) bit 23 (bit 12 is Categorical
-// with four), Binomial (id 13) bit 24 and Beta-Binomial (id 14) bit 25; the mask is an unsigned of 32 bits, so bits 26 .. 31 remain.
+// with four), Binomial (id 13) bit 24, Beta-Binomial (id 14) bit 25 and the zero-inflated Poisson (id 15) bit 26 (bit 15 is Categorical
+// with seven); the mask is an unsigned of 32 bits, so bits 27 .. 31 remain.
 static_assert(sizeof(unsigned) * 8 >= 32, "quad_multi mask");
 constexpr unsigned qm_bit(int lik, int dimf) {
   return lik == HMOGP_LIK_CATEGORICAL ? 1u << (8 + dimf)
@@ -420,6 +421,7 @@ constexpr unsigned qm_bit(int lik, int dimf) {
          : lik == HMOGP_LIK_WEIBULL ? 1u << 23
          : lik == HMOGP_LIK_BINOMIAL ? 1u << 24
          : lik == HMOGP_LIK_BETABINOMIAL ? 1u << 25
+         : lik == HMOGP_LIK_ZIPOISSON ? 1u << 26
                                       : (lik == HMOGP_LIK_STUDENT ? 1u << 17 : (lik == HMOGP_LIK_ORDINAL ? 1u << 18 : 1u << lik));
 }
 constexpr unsigned QM_C1 = qm_bit(HMOGP_LIK_HETGAUSSIAN, 0) | qm_bit(HMOGP_LIK_BERNOULLI, 0) | qm_bit(HMOGP_LIK_CATEGORICAL, 2);
@@ -464,7 +466,7 @@ __global__ __launch_bounds__(256) void quad_multi_kernel(QuadMulti m) {
   }
   QB(HMOGP_LIK_GAUSSIAN) QB(HMOGP_LIK_BERNOULLI) QB(HMOGP_LIK_HETGAUSSIAN) QB(HMOGP_LIK_POISSON) QB(HMOGP_LIK_EXPONENTIAL)
   QB(HMOGP_LIK_GAMMA) QB(HMOGP_LIK_BETA) QB(HMOGP_LIK_STUDENT) QB(HMOGP_LIK_ORDINAL) QB(HMOGP_LIK_NEGBINOMIAL)
-  QB(HMOGP_LIK_WEIBULL) QB(HMOGP_LIK_BINOMIAL) QB(HMOGP_LIK_BETABINOMIAL)
+  QB(HMOGP_LIK_WEIBULL) QB(HMOGP_LIK_BINOMIAL) QB(HMOGP_LIK_BETABINOMIAL) QB(HMOGP_LIK_ZIPOISSON)
   QBC(1) QBC(2) QBC(3) QBC(4) QBC(5) QBC(6) QBC(7) QBC(8)
 #define QBD(K)                                                 \
   if constexpr ((MASK & qm_bit(HMOGP_LIK_DIRICHLET, K)) != 0) { \
@@ -758,7 +760,7 @@ __global__ __launch_bounds__(256) void var_exp_kernel(int J, double param, long 
 #pragma unroll
   for (int j = 0; j < HMOGP_MAXJ; ++j) o.gm[j] = o.gv[j] = 0.0;
   const double yy = y[n];
-  const double yaux = (LIK == HMOGP_LIK_POISSON || LIK == HMOGP_LIK_NEGBINOMIAL)
+  const double yaux = (LIK == HMOGP_LIK_POISSON || LIK == HMOGP_LIK_NEGBINOMIAL || LIK == HMOGP_LIK_ZIPOISSON)
                           ? lgamma(yy + 1.0)
                           : ((LIK == HMOGP_LIK_ORDINAL || LIK == HMOGP_LIK_WEIBULL) ? y[N + n] : (lik_has_trials(LIK) ? y[2 * N + n] : 0.0));  // Ordinal, Weibull: y is [2][N]
   if constexpr (lik_has_trials(LIK)) param = y[N + n];   // Binomial, Beta-Binomial: y is [3][N] = (k, n, lc); the row's own n, not n*
@@ -821,7 +823,7 @@ __global__ __launch_bounds__(256) void log_predictive_kernel(int J, double param
     mu[j] = (j < J) ? m[n * J + j] : 0.0;
     sd[j] = (j < J) ? sqrt(v[n * J + j]) : 0.0;
   }
-  const double yy = y[n], yaux = (LIK == HMOGP_LIK_POISSON || LIK == HMOGP_LIK_NEGBINOMIAL)
+  const double yy = y[n], yaux = (LIK == HMOGP_LIK_POISSON || LIK == HMOGP_LIK_NEGBINOMIAL || LIK == HMOGP_LIK_ZIPOISSON)
                                      ? lgamma(yy + 1.0)
                                      : ((LIK == HMOGP_LIK_ORDINAL || LIK == HMOGP_LIK_WEIBULL) ? y[N + n] : (lik_has_trials(LIK) ? y[2 * N + n] : 0.0));
   if constexpr (lik_has_trials(LIK)) param = y[N + n];   // y is [3][N] = (k, n, lc)
@@ -994,6 +996,7 @@ void launch_sample(int lik, int J, double param, long long N, unsigned long long
     case HMOGP_LIK_WEIBULL: SK(HMOGP_LIK_WEIBULL); break;
     case HMOGP_LIK_BINOMIAL: SK(HMOGP_LIK_BINOMIAL); break;
     case HMOGP_LIK_BETABINOMIAL: SK(HMOGP_LIK_BETABINOMIAL); break;
+    case HMOGP_LIK_ZIPOISSON: SK(HMOGP_LIK_ZIPOISSON); break;
     case HMOGP_LIK_ORDINAL: hipLaunchKernelGGL(ordinal_sample_kernel, grid, dim3(256), 0, s, ordinal_table(param), N, seed, F, Y); break;
     case HMOGP_LIK_DIRICHLET:
       DISPATCH_DIRK(J, hipLaunchKernelGGL((dirichlet_sample_kernel<DK>), grid, dim3(256), 0, s, N, seed, F, Y));
@@ -1061,6 +1064,7 @@ void launch_quad(const QuadArgs& a, hipStream_t s) {
     case HMOGP_LIK_WEIBULL: QK(HMOGP_LIK_WEIBULL); break;
     case HMOGP_LIK_BINOMIAL: QK(HMOGP_LIK_BINOMIAL); break;
     case HMOGP_LIK_BETABINOMIAL: QK(HMOGP_LIK_BETABINOMIAL); break;
+    case HMOGP_LIK_ZIPOISSON: QK(HMOGP_LIK_ZIPOISSON); break;
     case HMOGP_LIK_ORDINAL: QK(HMOGP_LIK_ORDINAL); break;
     case HMOGP_LIK_DIRICHLET:
       DISPATCH_DIRK(a.dimf, hipLaunchKernelGGL((quad_kernel<HMOGP_LIK_DIRICHLET, DK>), grid, dim3(256), 0, s, a));
@@ -1113,7 +1117,7 @@ void launch_quad_multi(const QuadMulti& m_in, hipStream_t s) {
   QMS(QM_LIGHT)
   QMS(qm_bit(HMOGP_LIK_GAMMA, 0)) QMS(qm_bit(HMOGP_LIK_BETA, 0)) QMS(qm_bit(HMOGP_LIK_STUDENT, 0))
   QMS(qm_bit(HMOGP_LIK_ORDINAL, 0)) QMS(qm_bit(HMOGP_LIK_NEGBINOMIAL, 0)) QMS(qm_bit(HMOGP_LIK_WEIBULL, 0))
-  QMS(qm_bit(HMOGP_LIK_BINOMIAL, 0)) QMS(qm_bit(HMOGP_LIK_BETABINOMIAL, 0))
+  QMS(qm_bit(HMOGP_LIK_BINOMIAL, 0)) QMS(qm_bit(HMOGP_LIK_BETABINOMIAL, 0)) QMS(qm_bit(HMOGP_LIK_ZIPOISSON, 0))
   QMS(qm_bit(HMOGP_LIK_DIRICHLET, 2)) QMS(qm_bit(HMOGP_LIK_DIRICHLET, 3)) QMS(qm_bit(HMOGP_LIK_DIRICHLET, 4))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 1)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 2)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 3))
   QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 4)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 5)) QMS(qm_bit(HMOGP_LIK_CATEGORICAL, 6))
@@ -1153,6 +1157,7 @@ void launch_var_exp(int lik, int J, double param, long long N, const double* y, 
     case HMOGP_LIK_WEIBULL: VK(HMOGP_LIK_WEIBULL); break;
     case HMOGP_LIK_BINOMIAL: VK(HMOGP_LIK_BINOMIAL); break;
     case HMOGP_LIK_BETABINOMIAL: VK(HMOGP_LIK_BETABINOMIAL); break;
+    case HMOGP_LIK_ZIPOISSON: VK(HMOGP_LIK_ZIPOISSON); break;
     case HMOGP_LIK_ORDINAL: param = ordinal_table(param).sigma; VK(HMOGP_LIK_ORDINAL); break;
     case HMOGP_LIK_DIRICHLET:
       DISPATCH_DIRK(J, hipLaunchKernelGGL((var_exp_kernel<HMOGP_LIK_DIRICHLET, DK>), grid, dim3(256), 0, s, J, param, N, y, m, v, ve,
@@ -1183,6 +1188,7 @@ void launch_predictive(int lik, int J, int Jp, double param, int T, long long N,
     case HMOGP_LIK_WEIBULL: PK(HMOGP_LIK_WEIBULL); break;
     case HMOGP_LIK_BINOMIAL: PK(HMOGP_LIK_BINOMIAL); break;
     case HMOGP_LIK_BETABINOMIAL: PK(HMOGP_LIK_BETABINOMIAL); break;
+    case HMOGP_LIK_ZIPOISSON: PK(HMOGP_LIK_ZIPOISSON); break;
     case HMOGP_LIK_ORDINAL: hipLaunchKernelGGL(ordinal_predictive_kernel, grid, dim3(256), 0, s, ordinal_table(param), N, m, v, mean, var); break;
     case HMOGP_LIK_DIRICHLET:   // (64 lanes per row: the grid above is one block per 4 rows)
       DISPATCH_DIRK(J, hipLaunchKernelGGL((dirichlet_predictive_kernel<DK>), grid, dim3(256), 0, s, T, N, m, v, mean, var));
@@ -1209,6 +1215,7 @@ void launch_log_predictive(int lik, int J, double param, long long N, int S, uns
     case HMOGP_LIK_WEIBULL: LK(HMOGP_LIK_WEIBULL); break;
     case HMOGP_LIK_BINOMIAL: LK(HMOGP_LIK_BINOMIAL); break;
     case HMOGP_LIK_BETABINOMIAL: LK(HMOGP_LIK_BETABINOMIAL); break;
+    case HMOGP_LIK_ZIPOISSON: LK(HMOGP_LIK_ZIPOISSON); break;
     case HMOGP_LIK_ORDINAL: param = ordinal_table(param).sigma; LK(HMOGP_LIK_ORDINAL); break;
     case HMOGP_LIK_DIRICHLET:
       DISPATCH_DIRK(J, hipLaunchKernelGGL((dirichlet_log_predictive_kernel<DK>), grid, dim3(256), 0, s, N, S, seed, y, m, v, out));

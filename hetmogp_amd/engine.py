@@ -15,7 +15,7 @@ LIK_IDS = dict(Gaussian=_lib.LIK_GAUSSIAN, Bernoulli=_lib.LIK_BERNOULLI, HetGaus
                Categorical=_lib.LIK_CATEGORICAL, Poisson=_lib.LIK_POISSON, Exponential=_lib.LIK_EXPONENTIAL,
                Gamma=_lib.LIK_GAMMA, Beta=_lib.LIK_BETA, Student=_lib.LIK_STUDENT, Ordinal=_lib.LIK_ORDINAL,
                Dirichlet=_lib.LIK_DIRICHLET, NegBinomial=_lib.LIK_NEGBINOMIAL, Weibull=_lib.LIK_WEIBULL,
-               Binomial=_lib.LIK_BINOMIAL, BetaBinomial=_lib.LIK_BETABINOMIAL)
+               Binomial=_lib.LIK_BINOMIAL, BetaBinomial=_lib.LIK_BETABINOMIAL, ZIPoisson=_lib.LIK_ZIPOISSON)
 
 _TWO_COLUMN_Y = {"Weibull": "(time, event indicator)", "Binomial": "(successes k, trials n)", "BetaBinomial": "(successes k, trials n)"}
 
@@ -35,7 +35,7 @@ def lik_dim_f(name, **kw):
     if name == "Dirichlet":
         return int(kw["K"])
     return dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1,
-                NegBinomial=2, Weibull=2, Binomial=1, BetaBinomial=2)[name]
+                NegBinomial=2, Weibull=2, Binomial=1, BetaBinomial=2, ZIPoisson=2)[name]
 
 
 def lik_dim_y(name, **kw):
@@ -665,7 +665,8 @@ PREDQ_MISSING = {"Poisson": "a regularised incomplete gamma function", "Gamma": 
                  "Beta": "a regularised incomplete beta function", "Student": "a regularised incomplete beta function",
                  "NegBinomial": "a regularised incomplete beta function", "Categorical": "an order of its classes (it has none)",
                  "Dirichlet": "a univariate outcome (it is multivariate)",
-                 "Binomial": "a regularised incomplete beta function", "BetaBinomial": "a regularised incomplete beta function"}
+                 "Binomial": "a regularised incomplete beta function", "BetaBinomial": "a regularised incomplete beta function",
+                 "ZIPoisson": "a regularised incomplete gamma function"}
 
 
 def predq_require(name):

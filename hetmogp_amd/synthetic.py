@@ -5,7 +5,7 @@ conditioned at large M.  Used by bench.py, smoke() and the size-p
 import numpy as np
 
 _DIM_F = dict(Gaussian=1, Bernoulli=1, HetGaussian=2, Poisson=1, Exponential=1, Gamma=2, Beta=2, Student=2, Ordinal=1,
-              NegBinomial=2, Weibull=2, Binomial=1, BetaBinomial=2)
+              NegBinomial=2, Weibull=2, Binomial=1, BetaBinomial=2, ZIPoisson=2)
 
 
 def _dim_f(name, kw):
@@ -47,6 +47,10 @@ def _sample(rng, name, kw, F):
     if name == "NegBinomial":                  # Gamma-Poisson mixture: mean exp(f0), size exp(f1)
         r = np.exp(np.clip(F[:, 1:2], -2, 3))
         return rng.poisson(np.exp(np.clip(F[:, :1], -5, 3)) * rng.gamma(r) / r).astype(float)
+    if name == "ZIPoisson":                    # a structural zero with probability sigmoid(f1), else Poisson(exp(f0))
+        lam = np.exp(np.clip(F[:, :1], -5, 3))
+        zero = rng.rand(n, 1) < 1.0 / (1.0 + np.exp(-np.clip(F[:, 1:2], -3, 3)))
+        return np.where(zero, 0.0, rng.poisson(lam)).astype(float)
     if name == "Weibull":                      # (time, event indicator): censored at an independent Weibull censoring time
         return weibull_censored(rng, np.clip(F[:, :1], -3, 3), np.clip(F[:, 1:2], -1, 1.5), kw.get("censored", 0.3))
     if name in ("Binomial", "BetaBinomial"):   # (successes, trials): the trials drawn per row from kw["trials"] = (lo, hi), inclusive

@@ -49,8 +49,19 @@ enum {
   HMOGP_LIK_NEGBINOMIAL = 11, /* (not in the reference)  no param (0.0 is passed and ignored)  dim_f = 2 */
   HMOGP_LIK_WEIBULL = 12,     /* (not in the reference)  no param (0.0 is passed and ignored)  dim_f = 2, Y is [N, 2] */
   HMOGP_LIK_BINOMIAL = 13,    /* (not in the reference)  param = trial count n* of predictive / sample (0.0: 1)  dim_f = 1, Y is [N, 2] */
-  HMOGP_LIK_BETABINOMIAL = 14 /* (not in the reference)  param as Binomial's                                    dim_f = 2, Y is [N, 2] */
+  HMOGP_LIK_BETABINOMIAL = 14, /* (not in the reference)  param as Binomial's                                   dim_f = 2, Y is [N, 2] */
+  HMOGP_LIK_ZIPOISSON = 15    /* (not in the reference)  no param (0.0 is passed and ignored)  dim_f = 2 */
 };
+
+/* Zero-inflated Poisson: counts with more zeros than a rate explains.  f0 = log of the rate lambda (Poisson's link),
+ * f1 = logit of the structural-zero probability pi = clip(e^f1 / (1 + e^f1), 1e-9, 1 - 1e-9) (Bernoulli's link and clip):
+ *   p(0 | f) = pi + (1 - pi) exp(-lambda),     p(y | f) = (1 - pi) Poisson(y | lambda) for y >= 1.
+ * A row with y >= 1 is the sum of Poisson's 20-node rule over f0 and Bernoulli's (label 0) over f1; a row with y = 0 is the 20 x 20 rule.
+ * Y is one column of finite, non-negative, integer-valued doubles; anything else is HMOGP_E_INVALID ("ZIPoisson" in the message) in
+ * hmogp_set_task_data (the task keeps its previous data) and in every building block that takes y (hmogp_var_exp[_ex],
+ * hmogp_log_predictive, hmogp_log_predictive_gh), there before the device is asked for.  The family has no parameter of its own:
+ * hmogp_lik_param_count answers 0 and hmogp_var_exp_dparam refuses it.  The predictive cdf and quantiles are refused (they need the
+ * regularised incomplete gamma function, like Poisson's).  New enum value only: ABI version 8 stays. */
 
 /* Binomial and Beta-Binomial: k successes out of n trials, n the row's own.  Y is [N, 2] row-major: (k, n), both finite,
  * integer-valued doubles with 1 <= n <= 1e9 and 0 <= k <= n.  With lc = lgamma(n+1) - lgamma(k+1) - lgamma(n-k+1):
@@ -510,7 +521,7 @@ int hmogp_predict_log_density(hmogp_handle h, int32_t t, const double* Xnew, con
  *   Ordinal      closed form; y is the label c in 1 .. K (anything else: HMOGP_E_INVALID): P(Y <= c) = Phi((b_c - m) / sqrt(sigma^2 + v)), b_K = +inf
  *   Weibull      y is a TIME, [N] with no indicator column: (0, 1) for y <= 0, else k = shape(f1), z = min(k (log y - f0), 680), e = exp(z),
  *                S = exp(-e), C = -expm1(-e); the gh_T x gh_T tensor rule
- * Every other family is HMOGP_E_INVALID with the reason in the error string: Poisson and Gamma need a regularised incomplete gamma
+ * Every other family is HMOGP_E_INVALID with the reason in the error string: Poisson, ZIPoisson and Gamma need a regularised incomplete gamma
  * function, Beta, Student and NegBinomial a regularised incomplete beta function, Categorical has no order, Dirichlet is multivariate.
  * gh_T: 0 (= 20), 10 or 20.  y [N], m, v [N, dim_f]; cdf, sf [N], either may be NULL.
  * Quantiles: q[n, i] for the nP <= HMOGP_QUANT_MAXP probabilities p[i]; a p outside (0, 1) gives NaN in its column.  Bernoulli and

@@ -13,6 +13,9 @@
 //     32 MFMAs fed by 12 ds_read, 2-4 ds_write, one barrier -- no per-step bookkeeping;
 //   * [r7] the plain forward (rowpass_gemm_kernel<1>) takes C_q's fragments straight from L2 into registers and spends the LDS on
 //     an A image of BK = 32: 64 MFMAs fed by 32 ds_read + 16 buffer loads, 4 ds_write, one barrier (see "B DIRECT" below).
+//   * [r8] the Gram (rowpass_gemm_kernel<2>, gram_tile) takes the fragments of its UNSCALED operand straight from global memory
+//     and spends the LDS on a k-major image of the scaled one at BK = 32, wave tile 16 x 128: 64 MFMAs fed by 64 ds_read + 8
+//     buffer loads, 4 ds_write, one barrier (see "I DIRECT" below).
 #include <cstdlib>
 
 #include "common.h"
@@ -23,27 +26,27 @@ constexpr int BM = 128, BN = 128, BK = 16, W = 8, NT = W * 64;
 constexpr int KM_LD = 144, RM_LD = 18, TILE_DOUBLES = BK * KM_LD;   // LDS images: see gemm_f64.hip
 constexpr int NB = 2, WN = 32, NWN = 4;                              // wave tile 64 x 32 = 4 x 2 sub-tiles; 4 wave columns
 constexpr int BK32 = 32, A32_LD = 34, BD_D = 2;                      // plain forward, B direct: A image at BK = 32, B ring depth
+constexpr int GB = 8, GBG = 4, G_D = 2;                              // Gram: wave tile 16 x 128 = 1 x 8 sub-tiles, read in groups of 4; ring depth
 
 struct Tile {
   double a[2][TILE_DOUBLES];
   double b[2][TILE_DOUBLES];
 };
 
-// Diagonal tiles of the lower-only Gram: wave -> wave tile (wm, wn): (1,0) (1,1) (0,0) (1,2) (0,2) (0,3) (1,3) (0,1), i.e.
-// 8, 8, 7, 7, 0, 0, 3, 3 needed sub-tiles: the two waves of every SIMD (w and w + 4) carry 8, 8, 10, 10 instead of 16.
-__device__ __forceinline__ int diag_wm(int w) { return (0x4B >> w) & 1; }
-__device__ __forceinline__ int diag_wn(int w) { return (0x7E84 >> (2 * w)) & 3; }
+// Diagonal tiles of the lower-only Gram: wave w -> 16-row band wm of the tile, which needs the sub-tiles J <= wm, i.e. wm + 1 of 8.
+// Bands 7, 6, 5, 4, 0, 1, 2, 3: the two waves of every SIMD (w and w + 4) carry 8 + 1, 7 + 2, 6 + 3, 5 + 4 = 9 of the 36 needed
+// sub-tiles each, instead of 16.
+__device__ __forceinline__ int diag_wm(int w) { return w < 4 ? 7 - w : w - 4; }
 
-// One 128 x 128 tile of the contraction: main loop + epilogue (everything the kernel does once it knows its tile).
-template <int ROLE, bool FOLD = false, bool BD = false>
-__device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int ti, int tj, int split, Tile& lds, double* epi_a,
-                                             int* hwinfo = nullptr) {
+// One 128 x 128 tile of the forward contraction: main loop + epilogue (everything the kernel does once it knows its tile).
+template <bool FOLD = false, bool BD = false>
+__device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int ti, int tj, int split, Tile& lds, double* epi_a) {
   const int batch = blockIdx.z;
   const int M = g.M, N = g.N, K = g.K;
   const int i0 = ti * BM, j0 = tj * BN;
   if (i0 >= M || j0 >= N) return;
   int wlo = 0;
-  if (ROLE == 1 && g.b_tri > 0) wlo = j0;                      // triangular fold of C: op(B)[k][j] == 0 for k < j
+  if (g.b_tri > 0) wlo = j0;                                   // triangular fold of C: op(B)[k][j] == 0 for k < j
   const int ksteps = (K - wlo + BK - 1) / BK;
   const int per = (ksteps + g.ksplit - 1) / g.ksplit;
   const int kbeg = wlo + split * per * BK;
@@ -51,13 +54,13 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
 
   const double* __restrict__ A = g.A + (long long)batch * g.sA;
   const double* __restrict__ B = g.B + (long long)batch * g.sB;
-  const double* __restrict__ S = (ROLE == 2) ? g.kscale + (long long)batch * g.sS : nullptr;
   double* __restrict__ C = g.C + (long long)batch * g.sC + (long long)split * g.sSplit;
-  double* fs_part = (ROLE == 1 && g.fs_part) ? g.fs_part + (long long)batch * g.fs_sPart : nullptr;
+  double* fs_part = g.fs_part ? g.fs_part + (long long)batch * g.fs_sPart : nullptr;
 
   const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, lk = lane >> 4;
-  int wm = w >> 2, wn = w & 3;
+  const int wm = w >> 2;
+  int wn = w & 3;
   // [r5] Triangular fold: inside the DIAGONAL 128-row block of C's fold (k in [j0, j0 + 128)) the wave column wn only meets
   // non-zero entries from k = j0 + 32 wn on (op(B)[k][j] == 0 for k < j), so its MFMAs of the earlier k-steps are skipped: 8, 6,
   // 4, 2 of the block's 8 k-steps for wn = 0 .. 3 (products with exact zeros: the accumulators keep their bits).  Waves w and
@@ -65,27 +68,10 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
   // (FOLD: the paired kernel only -- the plain forward instantiation keeps its code)
   if (FOLD && w >= 4) wn = 3 - wn;
   const int klive = FOLD ? j0 + 32 * wn : 0;                    // first k-step whose MFMAs this wave issues
-  unsigned sub = 0xFFu;                                         // bit a*2 + b: sub-tile (a, b) of the wave tile is computed
-  const bool diag = ROLE == 2 && ti == tj && g.lower_only;
-  // Diagonal tiles: the four (w, w + 4) wave pairs carry 8, 8, 10, 10 of the 36 needed sub-tiles, and a pair shares a SIMD,
-  // so ONE block loads the CU's four SIMDs 8 : 8 : 10 : 10.  Two blocks are resident per CU: the one in the upper wave slots
-  // takes the pair types rotated by two (10 : 10 : 8 : 8 by PHYSICAL SIMD), which makes it 18 on every SIMD -- 9/16 of a
-  // full tile's MFMA time instead of 10/16.  HW_REG_HW_ID (tools/probes/probe_hwid.hip, gfx950): bits 5:4 = SIMD, bits 3:0 =
-  // wave slot on that SIMD (this kernel's 4 waves per SIMD sit in slots {0,1} / {2,3} by block).  Only the BALANCE depends on
-  // that reading: which wave computes which sub-tile does not change any value, and if the pairs are not found on four
-  // distinct SIMDs the static assignment is used.
-  if (diag && hwinfo) {
-    if (lane == 0) {
-      const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));   // HW_REG_HW_ID
-      hwinfo[w] = (int)((hw >> 4) & 3u);
-      if (w == 0) hwinfo[8] = (int)((hw >> 1) & 1u);                              // upper or lower pair of wave slots
-    }
-  }
   // The forward contraction accumulates the TRANSPOSED sub-tiles (MFMA operands swapped, B fragment columns permuted): lane
   // (lr, lk) register r of acc[a][b] holds P~[wm*64 + a*16 + lr][wn*32 + b*16 + 4*lk + r] -- a lane owns 4 adjacent columns
   // of ONE row, so the fused row statistics are in-lane sums + two shuffles and P~ leaves as 16-byte stores.
-  constexpr bool SWAP = (ROLE == 1);
-  const int blr = SWAP ? 4 * (lr & 3) + (lr >> 2) : lr;
+  const int blr = 4 * (lr & 3) + (lr >> 2);
 
   f64x4 acc[4][NB];
 #pragma unroll
@@ -94,51 +80,23 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
     for (int b = 0; b < NB; ++b) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
 
   // ---- operand streams: 4 doubles per thread, operand and k-step ------------------------------------------------------
-  // forward: A row-major (thread: row t/4, k's (t%4)*4..+3; rows beyond the matrix read the last row, never stored),
-  //          B k-major   (thread: k row t/32, column pairs (t%32)*2 and +64)
-  // Gram:    A and B k-major over the same rows (thread: k row t/32 ...); rows beyond the range get the k-scale 0
+  // A row-major (thread: row t/4, k's (t%4)*4..+3; rows beyond the matrix read the last row, never stored),
+  // B k-major   (thread: k row t/32, column pairs (t%32)*2 and +64)
   const int ar = t >> 2, ak = (t & 3) * 4, bk = t >> 5, bc = (t & 31) * 2;
-  const double* pa;
-  const double* pb;
-  if (ROLE == 1) {
-    pa = A + (long long)min(i0 + ar, M - 1) * g.lda + ak;
-    pb = B + (long long)bk * g.ldb + j0 + bc;
-  } else {
-    pa = A + i0 + bc;
-    pb = B + j0 + bc;
-  }
-  double ra[4], rb[4], ks = 1.0;
+  const double* pa = A + (long long)min(i0 + ar, M - 1) * g.lda + ak;
+  const double* pb = B + (long long)bk * g.ldb + j0 + bc;
+  double ra[4], rb[4];
   auto load = [&](int k0) {
-    if (ROLE == 1) {
-      const f64x2 x0 = *reinterpret_cast<const f64x2*>(pa + k0), x1 = *reinterpret_cast<const f64x2*>(pa + k0 + 2);
-      ra[0] = x0.x, ra[1] = x0.y, ra[2] = x1.x, ra[3] = x1.y;
-      const double* q = pb + (long long)k0 * g.ldb;
-      const f64x2 y0 = *reinterpret_cast<const f64x2*>(q), y1 = *reinterpret_cast<const f64x2*>(q + 64);
-      rb[0] = y0.x, rb[1] = y0.y, rb[2] = y1.x, rb[3] = y1.y;
-    } else {
-      const int row = k0 + bk;
-      const long long off = (long long)min(row, K - 1) * g.lda;
-      const f64x2 x0 = *reinterpret_cast<const f64x2*>(pa + off), x1 = *reinterpret_cast<const f64x2*>(pa + off + 64);
-      ra[0] = x0.x, ra[1] = x0.y, ra[2] = x1.x, ra[3] = x1.y;
-      const f64x2 y0 = *reinterpret_cast<const f64x2*>(pb + off), y1 = *reinterpret_cast<const f64x2*>(pb + off + 64);
-      rb[0] = y0.x, rb[1] = y0.y, rb[2] = y1.x, rb[3] = y1.y;
-      ks = (row < kend) ? S[row] : 0.0;
-    }
+    const f64x2 x0 = *reinterpret_cast<const f64x2*>(pa + k0), x1 = *reinterpret_cast<const f64x2*>(pa + k0 + 2);
+    ra[0] = x0.x, ra[1] = x0.y, ra[2] = x1.x, ra[3] = x1.y;
+    const double* q = pb + (long long)k0 * g.ldb;
+    const f64x2 y0 = *reinterpret_cast<const f64x2*>(q), y1 = *reinterpret_cast<const f64x2*>(q + 64);
+    rb[0] = y0.x, rb[1] = y0.y, rb[2] = y1.x, rb[3] = y1.y;
   };
-  // (the k-scale is applied at stage time, after the MFMA block: a multiply at load time makes the compiler wait for the
-  // loads in front of the MFMAs and exposes the HBM latency every k-step)
   auto stage = [&](int buf) {
-    if (ROLE == 1) {
-      double* sa = &lds.a[buf][ar * RM_LD + ak];
-      *reinterpret_cast<f64x2*>(sa) = f64x2{ra[0], ra[1]};
-      *reinterpret_cast<f64x2*>(sa + 2) = f64x2{ra[2], ra[3]};
-    } else {
-      double* sa = &lds.a[buf][bk * KM_LD + bc];
-      *reinterpret_cast<f64x2*>(sa) = f64x2{ra[0], ra[1]};
-      *reinterpret_cast<f64x2*>(sa + 64) = f64x2{ra[2], ra[3]};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rb[i] *= ks;
-    }
+    double* sa = &lds.a[buf][ar * RM_LD + ak];
+    *reinterpret_cast<f64x2*>(sa) = f64x2{ra[0], ra[1]};
+    *reinterpret_cast<f64x2*>(sa + 2) = f64x2{ra[2], ra[3]};
     double* sb = &lds.b[buf][bk * KM_LD + bc];
     *reinterpret_cast<f64x2*>(sb) = f64x2{rb[0], rb[1]};
     *reinterpret_cast<f64x2*>(sb + 64) = f64x2{rb[2], rb[3]};
@@ -146,10 +104,10 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
   // MFMA operands ("fragments") of one k4-step: 4 A values + NB B values per lane, read from the LDS images into register set s
   double fa[2][4], fb[2][NB];
   auto frag = [&](int buf, int kk, int s) {
-    const double* fpa = (ROLE == 1) ? &lds.a[buf][(wm * 64 + lr) * RM_LD + kk * 4 + lk] : &lds.a[buf][(kk * 4 + lk) * KM_LD + wm * 64 + lr];
+    const double* fpa = &lds.a[buf][(wm * 64 + lr) * RM_LD + kk * 4 + lk];
     const double* fpb = &lds.b[buf][(kk * 4 + lk) * KM_LD + wn * WN + blr];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) fa[s][i] = fpa[i * 16 * (ROLE == 1 ? RM_LD : 1)];
+    for (int i = 0; i < 4; ++i) fa[s][i] = fpa[i * 16 * RM_LD];
 #pragma unroll
     for (int i = 0; i < NB; ++i) fb[s][i] = fpb[i * 16];
   };
@@ -157,11 +115,7 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        if (ROLE == 2 && !((sub >> (a * NB + b)) & 1u)) continue;   // wave-uniform (scalar) guard; all set off the diagonal
-        acc[a][b] = SWAP ? __builtin_amdgcn_mfma_f64_16x16x4f64(fb[s][b], fa[s][a], acc[a][b], 0, 0, 0)
-                         : __builtin_amdgcn_mfma_f64_16x16x4f64(fa[s][a], fb[s][b], acc[a][b], 0, 0, 0);
-      }
+      for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[s][b], fa[s][a], acc[a][b], 0, 0, 0);
   };
 
   // ---- [r7] plain forward, B DIRECT (BD): C_q's fragments straight from L2 into registers, A image at BK = 32 ---------------
@@ -191,7 +145,7 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
   //   * same products in the same order per accumulator (k ascending, k4 grouping 4 kk + lk, operands swapped): P~, p and c are
   //     bit-identical to the staged loop.
   if constexpr (BD) {
-    static_assert(ROLE == 1 && !FOLD, "B direct: the plain forward only");
+    static_assert(!FOLD, "B direct: the plain forward only");
     constexpr int KS = BK32 / 4, NA = BK32 / 4;
     static_assert(KS % BD_D == 0, "static ring slots");
     static_assert(2 * BM * A32_LD <= 4 * TILE_DOUBLES, "A image at BK = 32 fits the tile buffers");
@@ -279,27 +233,6 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
     if (kbeg + BK < kend) load(kbeg + BK);
   }
   if (!BD) __syncthreads();
-  if (diag) {
-    int role = w;                                               // static assignment: pair type w & 3, half w >> 2
-    if (hwinfo) {
-      bool ok = true;
-      unsigned seen = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        ok = ok && hwinfo[i] == hwinfo[i + 4];
-        seen |= 1u << hwinfo[i];
-      }
-      if (ok && seen == 0xFu) role = ((hwinfo[w] + 2 * hwinfo[8]) & 3) + (w & 4);
-    }
-    role = __builtin_amdgcn_readfirstlane(role);
-    wm = diag_wm(role), wn = diag_wn(role);
-    sub = 0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < NB; ++b)
-        if (wn * NB + b <= wm * 4 + a) sub |= 1u << (a * NB + b);
-  }
   // [r4] Main loop with the fragments ONE k4-step AHEAD OF THE MFMAs AND CARRIED ACROSS THE BARRIER: the fragments of the next
   // tile's first k4-step are read right behind the barrier, in front of the last 8 MFMAs of the current tile, and the staging
   // of step k + 1 / the global loads of step k + 2 sit behind the first 8 MFMAs -- a wave never waits for LDS (or for the
@@ -307,28 +240,9 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
   // (tools/probes/probe_gemm_abl.hip, profiles/r04_gemm_ablation.txt): 66.3 -> 70.8 TFLOP/s; the same loop without any
   // barrier (racy) 72.5, MFMAs alone in this tile structure 73.6.  Same operations on the same values in the same order per
   // accumulator: results are bit-identical to the round-3 loop.
-  // The Gram keeps the round-3 loop (fragments read inside the step): the carried fragments cost 12 registers, the Gram's 112
-  // allocated registers are what lets the column statistics run BESIDE it (one 64-register guest wave per SIMD), and alone it
-  // gains nothing (62.2 -> 62.3 TFLOP/s; in the step 39.4 -> 42.9 ms without the guest).
-  const bool live = ROLE == 1 || sub != 0;                     // (waves of a diagonal tile without a sub-tile idle through it)
-  if (ROLE == 2) {
-    for (int k0 = kbeg; k0 < kend; k0 += BK) {
-      if (k0 + BK < kend) stage(cur ^ 1);
-      if (k0 + 2 * BK < kend) load(k0 + 2 * BK);
-      if (live) {
-#pragma unroll
-        for (int kk = 0; kk < BK / 4; ++kk) {
-          frag(cur, kk, 0);
-          mm8(0);
-        }
-      }
-      __syncthreads();
-      cur ^= 1;
-    }
-  }
-  if (ROLE == 1 && !BD && kbeg < kend && (!FOLD || kbeg >= klive)) frag(0, 0, 0);
+  if (!BD && kbeg < kend && (!FOLD || kbeg >= klive)) frag(0, 0, 0);
 #define HM_SB __builtin_amdgcn_sched_barrier(0)
-  for (int k0 = kbeg; ROLE == 1 && !BD && k0 < kend; k0 += BK) {
+  for (int k0 = kbeg; !BD && k0 < kend; k0 += BK) {
     const bool more = k0 + BK < kend;
     const bool lv = !FOLD || k0 >= klive;                      // (wave-uniform; always true outside the fold's diagonal block)
     if (lv) {
@@ -362,7 +276,7 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
 #undef HM_SB
 
   // ---- epilogue: D fragment of v_mfma_f64_16x16x4_f64: col = lane&15, row = (lane>>4) + 4*reg --------------------------
-  if (ROLE == 1 && fs_part && g.fs_sq) {
+  if (fs_part && g.fs_sq) {
     // [r5] strict q(f): the only statistic is rowsum(T .* T) of the product itself -- in-lane squares of the lane's 8 values per
     // slice + the two shuffles over the four lanes of a row; same partial layout as `c` below (slot 1 of [stat][4 tiles_n][M])
 #pragma unroll
@@ -378,7 +292,7 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
       if (lk == 0 && i0 + rl < M) fs_part[((long long)NWN * tiles_n + NWN * tj + wn) * M + (i0 + rl)] = sq;
     }
     if (!g.store_c) return;
-  } else if (ROLE == 1 && fs_part) {
+  } else if (fs_part) {
     // Fused row statistics (GemmArgs::fs_*): lane (lr, lk) owns row rl = wm*64 + a*16 + lr and the column quads
     // wn*32 + b*16 + 4*lk + (0..3), b < 2, of slice a; it re-reads exactly its own 8 values of the K^ tile per slice
     // (L2/MALL-warm) with LDS-DMA loads (global_load_lds_dwordx4: lane l's 16 bytes land at base + 16*l) into a
@@ -445,45 +359,178 @@ __device__ __forceinline__ void rowpass_tile(const GemmArgs& g, int tiles_n, int
     }
     if (!g.store_c) return;
   }
-  if (SWAP) {  // lane (lr, lk): row wm*64 + a*16 + lr, columns wn*32 + b*16 + 4*lk + (0..3)
+  // lane (lr, lk): row wm*64 + a*16 + lr, columns wn*32 + b*16 + 4*lk + (0..3)
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int row = i0 + wm * 64 + a * 16 + lr;
-      if (row >= M) continue;
-      double* crow = C + (long long)row * g.ldc + j0 + wn * WN + 4 * lk;
-      if (g.c_sub) {   // [r5] C -= op(A) op(B): the 128-column updates of the strict mode's blocked triangular solves
-        // (c_src: the columns' FIRST touch reads them from the matrix the solve started from -- no copy of it beforehand)
-        const double* srow = g.c_src ? g.c_src + (long long)batch * g.sC + (long long)row * g.ldc + j0 + wn * WN + 4 * lk : crow;
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const f64x2 c01 = *reinterpret_cast<const f64x2*>(srow + b * 16), c23 = *reinterpret_cast<const f64x2*>(srow + b * 16 + 2);
-          *reinterpret_cast<f64x2*>(crow + b * 16) = f64x2{c01.x - acc[a][b][0], c01.y - acc[a][b][1]};
-          *reinterpret_cast<f64x2*>(crow + b * 16 + 2) = f64x2{c23.x - acc[a][b][2], c23.y - acc[a][b][3]};
-        }
-        continue;
-      }
+  for (int a = 0; a < 4; ++a) {
+    const int row = i0 + wm * 64 + a * 16 + lr;
+    if (row >= M) continue;
+    double* crow = C + (long long)row * g.ldc + j0 + wn * WN + 4 * lk;
+    if (g.c_sub) {   // [r5] C -= op(A) op(B): the 128-column updates of the strict mode's blocked triangular solves
+      // (c_src: the columns' FIRST touch reads them from the matrix the solve started from -- no copy of it beforehand)
+      const double* srow = g.c_src ? g.c_src + (long long)batch * g.sC + (long long)row * g.ldc + j0 + wn * WN + 4 * lk : crow;
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        *reinterpret_cast<f64x2*>(crow + b * 16) = f64x2{acc[a][b][0], acc[a][b][1]};
-        *reinterpret_cast<f64x2*>(crow + b * 16 + 2) = f64x2{acc[a][b][2], acc[a][b][3]};
+        const f64x2 c01 = *reinterpret_cast<const f64x2*>(srow + b * 16), c23 = *reinterpret_cast<const f64x2*>(srow + b * 16 + 2);
+        *reinterpret_cast<f64x2*>(crow + b * 16) = f64x2{c01.x - acc[a][b][0], c01.y - acc[a][b][1]};
+        *reinterpret_cast<f64x2*>(crow + b * 16 + 2) = f64x2{c23.x - acc[a][b][2], c23.y - acc[a][b][3]};
       }
+      continue;
     }
-    return;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      *reinterpret_cast<f64x2*>(crow + b * 16) = f64x2{acc[a][b][0], acc[a][b][1]};
+      *reinterpret_cast<f64x2*>(crow + b * 16 + 2) = f64x2{acc[a][b][2], acc[a][b][3]};
+    }
   }
+}
+
+// One 128 x 128 tile of one row range of the weighted Gram H += A^T diag(s) B (both operands k-major over the same rows): main
+// loop + slab store.
+// ---- [r8] I DIRECT: the unscaled operand's fragments straight from global memory, the scaled one as an image at BK = 32 --------
+// For a fixed row k the 16 lanes lr of a fragment read 16 adjacent doubles of a k-major operand as they lie in memory: registers
+// -> ds_write -> ds_read was a copy for either operand.  With the i-side (MFMA operand A, unscaled) direct, the tile buffers
+// hold the j-side s_k b_kj as ONE double-buffered k-major image of 32 rows (2 x 32 x KM_LD doubles: the footprint of the two
+// BK = 16 image pairs it replaces): one block barrier per 64 MFMAs per wave instead of one per 32.
+// tools/probes/probe_gram_direct.hip, profiles/r08_gram_direct.txt (2 M rows streamed from HBM): 68.2 -> 70.5 TFLOP/s.
+//   * wave tile 16 x 128 (one sub-tile of the i-side, GB = 8 of the j-side; 8 x 1 wave tiles): the eight waves load disjoint
+//     16-column bands of the direct operand -- ONE load and a ring of G_D doubles per k4-step, no panel byte fetched twice by a
+//     block.  The image costs eight ds_read_b64 per k4-step (dword 288 lk + 2 lr + const: the half waves lk in {0, 1} / {2, 3}
+//     hit 64 distinct banks, as before), read in two groups of GBG = 4 in front of their 4 MFMAs (8 fragment registers, not 16).
+//     In the step: 32 x 64 with two loads per k4-step -0.5 ms, 64 x 32 with four over the register cap.
+//   * direct loads: lane (lr, lk) of band wm loads A[(k + lk) lda + i0 + 16 wm + lr] for the k4-step at k as one
+//     buffer_load_dwordx2 -- the lane part of the address in a VGPR, (k - kbeg) lda in an SGPR.
+//     The resource is based at the block's first row of its range and its column panel, so 32-bit byte offsets only have to span
+//     ONE RANGE (gemm_rowpass_eligible checks that).  The loads run G_D = 2 k4-steps ahead of the MFMAs that consume them: the
+//     load of step s + 2 is issued right behind the 8 MFMAs of step s into the slot those have read.
+//   * image: a thread stages 4 doubles of k row t/32 of each 16-row HALF of the step; half h of step s + 1 is loaded four k4-steps
+//     ahead of its ds_write into the ONE set of staging registers (4 doubles + the k-scale): h = 0 is written behind the first 8
+//     MFMAs of step s and the registers refilled with h = 1, which is written behind the fifth 8 and the registers refilled with
+//     h = 0 of step s + 2.  The lead of the BK = 16 loop at 10 staging registers instead of 18.  The k-scale is applied at stage
+//     time (a multiply at load time makes the compiler wait for the loads in front of the MFMAs).
+//   * no conditional load: image rows beyond the range read row min(row, K - 1) and get the k-scale 0 (so does the second half
+//     of a step when the range ends on an odd multiple of 16: range boundaries are NOT moved); direct loads beyond the range's
+//     last k4-step re-read it (consumed against the zero scale or not at all).  Where that last k4-step is the matrix's ragged
+//     one (K % 4 != 0) the lane rows are clamped to K - 1: a second lane offset, selected on a scalar condition.  The compiler
+//     derives counted s_waitcnt vmcnt(n) from the straight-line code: there is no vmcnt(0) in the loop (ISA checked).
+//   * same products a_ki (s_k b_kj) in the same order per accumulator (k ascending from kbeg, k4 grouping 4 kk + lk; the added
+//     half step contributes a * 0 to sums that start from + 0): H is bit-identical to the BK = 16 loop.
+__device__ __forceinline__ void gram_tile(const GemmArgs& g, int ti, int tj, int split, Tile& lds) {
+  const int batch = blockIdx.z;
+  const int M = g.M, N = g.N, K = g.K;
+  const int i0 = ti * BM, j0 = tj * BN;
+  if (i0 >= M || j0 >= N) return;
+  const int ksteps = (K + BK - 1) / BK;
+  const int per = (ksteps + g.ksplit - 1) / g.ksplit;
+  const int kbeg = split * per * BK;
+  const int kend = min(K, kbeg + per * BK);
+
+  const double* __restrict__ A = g.A + (long long)batch * g.sA;
+  const double* __restrict__ B = g.B + (long long)batch * g.sB;
+  const double* __restrict__ S = g.kscale + (long long)batch * g.sS;
+  double* __restrict__ C = g.C + (long long)batch * g.sC + (long long)split * g.sSplit;
+
+  const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int lr = lane & 15, lk = lane >> 4;
+  // (diagonal tiles: 9 needed sub-tiles per SIMD -- see diag_wm; only what lies on or below the diagonal is computed and stored)
+  const bool diag = ti == tj && g.lower_only;
+  const int wm = diag ? diag_wm(w) : w;                        // the wave's 16-row band of the tile
+  const int nsub = diag ? wm + 1 : GB;                         // sub-tiles 0 .. nsub - 1 of the band are computed (wave-uniform)
+
+  f64x4 acc[GB];
 #pragma unroll
-  for (int a = 0; a < 4; ++a)
+  for (int b = 0; b < GB; ++b) acc[b] = f64x4{0.0, 0.0, 0.0, 0.0};
+
+  // image operand: thread = k row t/32 of each half, column pairs (t%32)*2 and + 64
+  constexpr int KS = BK32 / 4, HALF = BK32 / 2;
+  static_assert(KS % G_D == 0, "static ring slots");
+  static_assert(2 * BK32 * KM_LD == 4 * TILE_DOUBLES, "the image at BK = 32 is the tile buffers");
+  double* const img = &lds.a[0][0];                            // [2][BK32 * KM_LD]
+  const int bk = t >> 5, bc = (t & 31) * 2;
+  const double* pst = B + j0 + bc;
+  double rs[4], ks;
+  auto loadh = [&](int k0, int h) {
+    const int row = min(k0 + HALF * h + bk, K - 1);
+    const long long off = (long long)row * g.ldb;
+    const f64x2 x0 = *reinterpret_cast<const f64x2*>(pst + off), x1 = *reinterpret_cast<const f64x2*>(pst + off + 64);
+    rs[0] = x0.x, rs[1] = x0.y, rs[2] = x1.x, rs[3] = x1.y;
+    ks = S[row];
+  };
+  auto stageh = [&](int buf, int k0, int h) {
+    const double sc = (k0 + HALF * h + bk < kend) ? ks : 0.0;
+    double* s = img + buf * (BK32 * KM_LD) + (HALF * h + bk) * KM_LD + bc;
+    *reinterpret_cast<f64x2*>(s) = f64x2{rs[0] * sc, rs[1] * sc};
+    *reinterpret_cast<f64x2*>(s + 64) = f64x2{rs[2] * sc, rs[3] * sc};
+  };
+  // direct operand (on diagonal tiles the same panel as the image's: no special case)
+  const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<double*>(A + (long long)kbeg * g.lda + i0), 0, (int)sizeof(double) * ((kend - 1 - kbeg) * g.lda + BM), 0x00020000);
+  const int klim = kbeg + 4 * ((kend - kbeg - 1) / 4);          // the range's last k4-step
+  const int avo = (int)sizeof(double) * (lk * g.lda + wm * 16 + lr);
+  const int avo_last = (int)sizeof(double) * (min(lk, K - 1 - klim) * g.lda + wm * 16 + lr);
+  double ga[G_D];
+  auto aload = [&](int k, int slot) {
+    const int so = __builtin_amdgcn_readfirstlane((min(k, klim) - kbeg) * g.lda * (int)sizeof(double));
+    ga[slot] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(ars, (k >= klim) ? avo_last : avo, so, 0));
+  };
+  if (kbeg < kend) {                                            // (an empty range loads nothing and still writes its zero slab tile)
+    loadh(kbeg, 0);
+    stageh(0, kbeg, 0);
+    loadh(kbeg, 1);
+    stageh(0, kbeg, 1);
+    loadh(kbeg + BK32, 0);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      double* crow = C + (long long)(i0 + wm * 64 + a * 16 + 4 * r + lk) * g.ldc + j0 + wn * WN + lr;
+    for (int d = 0; d < G_D; ++d) aload(kbeg + 4 * d, d);
+  }
+  __syncthreads();
+  {
+    int cur = 0;
+    for (int k0 = kbeg; k0 < kend; k0 += BK32) {
 #pragma unroll
-      for (int b = 0; b < NB; ++b)
-        if ((sub >> (a * NB + b)) & 1u) crow[b * 16] = acc[a][b][r];   // (diagonal tiles: only what lies on or below the diagonal)
+      for (int kk = 0; kk < KS; ++kk) {
+#pragma unroll
+        for (int gq = 0; gq < GB / GBG; ++gq) {
+          if (gq * GBG >= nsub) continue;                      // (a band of a diagonal tile that ends in the first group)
+          double fb[GBG];
+          const double* fpb = img + cur * (BK32 * KM_LD) + (kk * 4 + lk) * KM_LD + gq * 16 * GBG + lr;
+#pragma unroll
+          for (int b = 0; b < GBG; ++b) fb[b] = fpb[b * 16];
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int b = 0; b < GBG; ++b) {
+            if (gq * GBG + b >= nsub) continue;                // wave-uniform (scalar) guard; never taken off the diagonal
+            acc[gq * GBG + b] = __builtin_amdgcn_mfma_f64_16x16x4f64(ga[kk % G_D], fb[b], acc[gq * GBG + b], 0, 0, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        aload(k0 + 4 * (kk + G_D), kk % G_D);
+        if (kk == 0) {
+          stageh(cur ^ 1, k0 + BK32, 0);
+          loadh(k0 + BK32, 1);
+        }
+        if (kk == KS / 2) {
+          stageh(cur ^ 1, k0 + BK32, 1);
+          loadh(k0 + 2 * BK32, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __syncthreads();
+      cur ^= 1;
     }
+  }
+
+  // ---- slab store: D fragment of v_mfma_f64_16x16x4_f64: col = lane&15, row = (lane>>4) + 4*reg ------------------------------
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double* crow = C + (long long)(i0 + wm * 16 + 4 * r + lk) * g.ldc + j0 + lr;
+#pragma unroll
+    for (int b = 0; b < GB; ++b)
+      if (b < nsub) crow[b * 16] = acc[b][r];
+  }
 }
 
 template <int ROLE, bool PAIR, bool BD = false>
-__device__ __forceinline__ void rowpass_block(const GemmArgs& g, int tiles_n, int ntiles, Tile& lds, double* epi_a,
-                                              int* hwinfo = nullptr) {
+__device__ __forceinline__ void rowpass_block(const GemmArgs& g, int tiles_n, int ntiles, Tile& lds, double* epi_a) {
 
   // ---- which tile / batch / k-range (block b is observed to run on XCD b % 8: speed only) ----------------------------
   int v = blockIdx.x, split = 0;
@@ -527,13 +574,18 @@ __device__ __forceinline__ void rowpass_block(const GemmArgs& g, int tiles_n, in
     ti = v / tcols;
     tj = v - ti * tcols;
   }
-  rowpass_tile<ROLE, PAIR, BD>(g, tiles_n, ti, tj, split, lds, epi_a, hwinfo);
+  if constexpr (ROLE == 2) {
+    gram_tile(g, ti, tj, split, lds);
+    return;
+  } else {
+    rowpass_tile<PAIR, BD>(g, tiles_n, ti, tj, split, lds, epi_a);
+  }
   // Triangular fold (b_tri > 0, the E-step's / predict_f's forward): the k-loop of column tile j starts at j, so the tiles of
   // a row panel do 8, 7, ... 1 eighths of a full tile's work.  In paired mode a block takes column tiles j and
   // tiles_n - 1 - j one after the other: every block does (tiles_n + 1) / tiles_n of a full tile -- equal durations.
   if (PAIR) {
     __syncthreads();                 // the epilogue of the first tile used the tile buffers as scratch
-    rowpass_tile<ROLE, PAIR>(g, tiles_n, ti, tiles_n - 1 - tj, split, lds, epi_a);
+    rowpass_tile<PAIR>(g, tiles_n, ti, tiles_n - 1 - tj, split, lds, epi_a);
   }
 }
 
@@ -542,8 +594,7 @@ template <int ROLE>
 __global__ __launch_bounds__(NT, 4) void rowpass_gemm_kernel(GemmArgs g, int tiles_n, int ntiles) {
   __shared__ __attribute__((aligned(16))) Tile lds;
   __shared__ __attribute__((aligned(16))) double epi_a[ROLE == 1 ? 128 : 2];
-  __shared__ int hwinfo[ROLE == 2 ? 16 : 1];
-  rowpass_block<ROLE, false, ROLE == 1>(g, tiles_n, ntiles, lds, epi_a, ROLE == 2 ? hwinfo : nullptr);   // (forward: B direct)
+  rowpass_block<ROLE, false, ROLE == 1>(g, tiles_n, ntiles, lds, epi_a);   // (forward: B direct)
 }
 // the forward contraction with BOTH operands staged through LDS (BK = 16): the C -= A B updates of the strict solves (k-extents
 // that are multiples of 16 only), the unpaired triangular fold, B panels beyond 32-bit byte offsets
@@ -577,9 +628,12 @@ bool gemm_rowpass_eligible(const GemmArgs& g) {
   if (g.role == 1)
     return !g.a_kmajor && g.b_kmajor && !g.lower_only && g.ksplit == 1 && !g.kscale && g.b_tri >= 0 && (g.N % BN) == 0 &&
            (g.K % BK) == 0 && (g.K == g.N || sub) && g.K >= BK && g.M >= 1;
-  if (g.role == 2)
+  if (g.role == 2) {
+    // (the direct operand is addressed with 32-bit byte offsets from the first row of a block's row range: see gram_tile)
+    const long long per = (((long long)g.K + BK - 1) / BK + g.ksplit - 1) / g.ksplit;
     return g.a_kmajor && g.b_kmajor && g.kscale && g.b_tri == 0 && g.M == g.N && (g.N % BN) == 0 &&
-           g.lda == g.ldb && g.K >= 1;
+           g.lda == g.ldb && g.K >= 1 && g.ksplit >= 1 && ((per * BK + 4) * g.lda + BM) * (long long)sizeof(double) <= 0x7FFFFFFFLL;
+  }
   return false;
 }
 

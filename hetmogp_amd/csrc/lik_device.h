@@ -1272,7 +1272,9 @@ __device__ __forceinline__ double lik_sample(RowRng& g, const double* f, double 
   } else if (LIK == HMOGP_LIK_BETA) {
     const double a = clip(safe_exp(f[0]), 1e-9, 1e9), b = clip(safe_exp(f[1]), 1e-9, 1e9);
     const double x = g.gamma(a), yv = g.gamma(b);
-    return x / (x + yv);
+    // (both variates underflow where a and b are tiny, from e^f near 7e-3 down: 0 / 0.  The mass sits on 0 and 1 there, 1 with probability
+    // a / (a + b), the limit of the law -- as in the Beta-Binomial and Dirichlet draws below)
+    return x + yv > 0.0 ? x / (x + yv) : (g.uniform() * (a + b) < a ? 1.0 : 0.0);
   } else if (LIK == HMOGP_LIK_STUDENT) {  // location + scale * t(nu):  z / sqrt(chi2_nu / nu),  chi2_nu = 2 Gamma(nu/2, 1)
     const double z = g.normal(), G = g.gamma(0.5 * param);
     return f[0] + safe_exp(0.5 * f[1]) * z * sqrt(param / (2.0 * G));

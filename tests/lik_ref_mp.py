@@ -294,3 +294,101 @@ def var_exp(name, y, m, v, exact=False, **kw):
     out = [row_both(name, float(y[n]), [float(a) for a in m[n]], [float(a) for a in v[n]], **kw) for n in range(y.shape[0])]
     k = 2 if exact else 0
     return np.array([o[k] for o in out]).reshape(-1, 1 + 2 * J), np.array([o[k + 1] for o in out]).reshape(-1, 1 + 2 * J)
+
+
+# ---------------------------------------------------------------------------------------------- predictive moments (DESIGN 9o)
+# `<likelihood>.predictive(m, v)` node by node: per output element (the mean of every column, then the variance of every column) the value R
+# of the reference's rule and its condition scale S = sum over nodes of weight * sum |addends as the formula writes them|; the variance's S
+# includes the subtracted square of the mean.  Student is the closed form of DESIGN 9, NaN / +inf where the moment does not exist.
+def _sub_square(var, mean_r, square=lambda a: a * a):
+    var.add(1, -square(mean_r))
+    return var
+
+
+def predictive_row(name, m, v, T=20, sigma=0.5, deg_free=5.0, K=None):
+    """[mean_0 .., var_0 ..] as Acc of one row; T is the Gauss-Hermite order (unused by Gaussian and Student; Categorical always 10)."""
+    m, v = [mpf(a) for a in m], [mpf(a) for a in v]
+    mean, var = Acc(), Acc()
+    if name == "Gaussian":
+        mean.add(1, m[0])
+        var.add(1, mpf(float(sigma)) ** 2, v[0])
+        return [mean, var]
+    if name == "Student":
+        nu = mpf(float(deg_free))
+        if nu > 1:
+            mean.add(1, m[0])
+        else:
+            mean.r = mean.s = mpf("nan")
+        if nu > 2:
+            var.add(1, v[0], nu / (nu - 2) * mpmath.exp(m[1] + v[1] / 2))
+        else:
+            var.r = var.s = mpf("inf")
+        return [mean, var]
+    if name == "Categorical":
+        D = K - 1
+        x, w = gh(10)
+        E = [[safe_exp(_f(m[k], v[k], xi)) for xi in x] for k in range(D)]
+        means = [Acc() for _ in range(D)]
+        for idx in itertools.product(range(10), repeat=D):
+            ww = mpf(1)
+            for i in idx:
+                ww *= w[i]
+            e = [E[k][idx[k]] for k in range(D)]
+            den = 1 + sum(e)
+            rho = [clip(ek / den, PLO, PHI) for ek in e]
+            rs = sum(rho)
+            for d in range(D):
+                means[d].add(ww, rho[d] / rs)
+        return means + [Acc() for _ in range(D)]              # the reference's variance: zeros
+    x, w = gh(T)
+    if name == "HetGaussian":
+        mean.add(1, m[0])
+        for xi, wi in zip(x, w):
+            var.add(wi, safe_exp(_f(m[1], v[1], xi)), safe_square(_f(m[0], v[0], xi)))
+        return [mean, _sub_square(var, m[0])]
+    if name in ("Bernoulli", "Poisson", "Exponential"):
+        for xi, wi in zip(x, w):
+            f = _f(m[0], v[0], xi)
+            if name == "Bernoulli":
+                ef = safe_exp(f)
+                p = clip(ef / (1 + ef), PLO, PHI)
+                mu, vr, ms = p, p * (1 - p), p * p
+            elif name == "Poisson":
+                ef = safe_exp(f)
+                mu, vr, ms = ef, ef, ef * ef
+            else:
+                b = clip(safe_exp(-f), LO, HI)
+                mu, vr, ms = b, safe_square(b), safe_square(b)
+            mean.add(wi, mu)
+            var.add(wi, vr, ms)
+        return [mean, _sub_square(var, mean.r)]
+    if name in ("Gamma", "Beta"):                            # quirk Q1: the weight is w_i w_j / pi
+        A, B, wq = _tab2(m, v, T)
+        for a, wi in zip(A, wq):
+            for b, wj in zip(B, wq):
+                ww = wi * wj
+                if name == "Gamma":
+                    mu, vr = a / b, a / (b * b)
+                else:
+                    mu, vr = a / (a + b), a * b / ((a + b) * (a + b) * (a + b + 1))
+                mean.add(ww, mu)
+                var.add(ww, vr, mu * mu)
+        return [mean, _sub_square(var, mean.r, safe_square)]
+    raise KeyError(name)
+
+
+def predictive_row_f64(name, m, v, T=20, **kw):
+    """(R, S, real): float64 vectors of one row, and per element whether the rule's value is a real number (False: NaN / inf by the
+    contract itself, Student's missing moments) -- a real value that float64 cannot hold comes back as +-inf in R."""
+    kw = {k: a for k, a in kw.items() if a is not None}
+    acc = predictive_row(name, m, v, T, **kw)
+    R, S = _vec(acc)
+    return R, S, np.array([bool(mpmath.isfinite(a.r)) for a in acc])
+
+
+def predictive(name, m, v, T=20, **kw):
+    """m, v [N, J] -> R, S [N, 2 Jp] (Jp = K - 1 for Categorical, else 1): the means, then the variances."""
+    J = dim_f(name, **kw)
+    m, v = np.asarray(m, float).reshape(-1, J), np.asarray(v, float).reshape(-1, J)
+    out = [predictive_row_f64(name, [float(a) for a in m[n]], [float(a) for a in v[n]], T, **kw) for n in range(m.shape[0])]
+    return np.array([o[0] for o in out]), np.array([o[1] for o in out])

@@ -841,7 +841,7 @@ __global__ __launch_bounds__(256) void log_predictive_kernel(int J, double param
     if (l > mx) {
       se = se * exp(mx - l) + 1.0;
       mx = l;
-    } else {
+    } else if (l != -INFINITY) {  // a sample with p = 0 contributes nothing (-inf - -inf would be NaN); a NaN l still reaches se
       se += exp(l - mx);
     }
   }
@@ -849,7 +849,8 @@ __global__ __launch_bounds__(256) void log_predictive_kernel(int J, double param
   for (int o = 32; o > 0; o >>= 1) {  // combine (max, sumexp) pairs across the wave
     const double omx = __shfl_xor(mx, o, 64), ose = __shfl_xor(se, o, 64);
     const double nm = fmax(mx, omx);
-    se = (mx == -INFINITY ? 0.0 : se * exp(mx - nm)) + (omx == -INFINITY ? 0.0 : ose * exp(omx - nm));
+    // the side that holds the new maximum keeps its sum as it is (-inf == -inf too: an empty lane keeps its 0, a NaN lane its NaN)
+    se = (mx == nm ? se : se * exp(mx - nm)) + (omx == nm ? ose : ose * exp(omx - nm));
     mx = nm;
   }
   if (lane == 0) out[n] = -log((double)S) + mx + log(se);
@@ -937,7 +938,7 @@ __global__ __launch_bounds__(256) void dirichlet_log_predictive_kernel(long long
     if (l > mx) {
       se = se * exp(mx - l) + 1.0;
       mx = l;
-    } else {
+    } else if (l != -INFINITY) {  // as in log_predictive_kernel
       se += exp(l - mx);
     }
   }
@@ -945,7 +946,8 @@ __global__ __launch_bounds__(256) void dirichlet_log_predictive_kernel(long long
   for (int o = 32; o > 0; o >>= 1) {
     const double omx = __shfl_xor(mx, o, 64), ose = __shfl_xor(se, o, 64);
     const double nm = fmax(mx, omx);
-    se = (mx == -INFINITY ? 0.0 : se * exp(mx - nm)) + (omx == -INFINITY ? 0.0 : ose * exp(omx - nm));
+    // the side that holds the new maximum keeps its sum as it is (-inf == -inf too: an empty lane keeps its 0, a NaN lane its NaN)
+    se = (mx == nm ? se : se * exp(mx - nm)) + (omx == nm ? ose : ose * exp(omx - nm));
     mx = nm;
   }
   if (lane == 0) out[n] = -log((double)S) + mx + log(se);

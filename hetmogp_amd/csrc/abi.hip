@@ -363,6 +363,23 @@ int hmogp_predict_f(hmogp_handle h, const double* Xnew, int64_t Nnew, double* m,
   return guarded(h, [&] { h->predict_f(Xnew, Nnew, m, v); });
 }
 
+int hmogp_predict_f_joint(hmogp_handle h, const double* Xnew, int64_t Nnew, int32_t nD, const int32_t* d_index, double* mean, double* cov) {
+  if (!h) return HMOGP_E_INVALID;
+  return guarded(h, [&] { h->joint(Xnew, Nnew, nD, d_index, mean, cov, 0, 0, nullptr, nullptr, nullptr, nullptr); });
+}
+
+int hmogp_sample_f_joint(hmogp_handle h, const double* Xnew, int64_t Nnew, int32_t nD, const int32_t* d_index, int32_t S, uint64_t seed,
+                         double* F, double* mean, double* L, double* jitter_out, int32_t* rung_out) {
+  if (!h) return HMOGP_E_INVALID;
+  return guarded(h, [&] {
+    if (S < 1) {      // (behind the state check, like every other refusal)
+      if (!h->evaluated && !h->began) throw EngineError{HMOGP_E_STATE, "no evaluation to predict from"};
+      throw EngineError{HMOGP_E_INVALID, "joint: S must be >= 1"};
+    }
+    h->joint(Xnew, Nnew, nD, d_index, mean, nullptr, S, seed, F, L, jitter_out, rung_out);
+  });
+}
+
 int hmogp_last_timings(hmogp_handle h, double* out_ms, int64_t* launches) {
   if (!h || !out_ms) return HMOGP_E_INVALID;
   for (int c = 0; c < NCAT; ++c) {

@@ -553,6 +553,10 @@ struct hmogp_engine {
   // q != nullptr: quantiles of the nP probabilities p, else cdf / sf (either may be null) of ynew
   void predict_cdf_quantile(int t, const double* Xnew, const double* ynew, long long Nnew, int T, double* cdf, double* sf, int nP,
                             const double* p, double* q);
+  // joint mean / covariance of the functions d[0 .. nD) at Xnew; with S > 0 also the factor of cov + jitter I on the jitchol
+  // ladder and S draws F = mean + L z.  mean, cov, L, jitter_out, rung_out may be null where the caller does not want them.
+  void joint(const double* Xnew, long long Nnew, int nD, const int* d, double* mean, double* cov, int S, unsigned long long seed,
+             double* F, double* Lout, double* jitter_out, int* rung_out);
 
   // ---- likelihood parameters (lik_param.hip) ----
   bool lik_grad_on = false;      // hmogp_lik_grad_enable: persistent

@@ -323,3 +323,122 @@ void hmogp_engine::predict_cdf_quantile(int t, const double* Xnew, const double*
   if (!quant && cdf) HIP_TRY(hipMemcpy(cdf, d1.p, sizeof(double) * Nnew, hipMemcpyDeviceToHost));
   if (!quant && sf) HIP_TRY(hipMemcpy(sf, d2.p, sizeof(double) * Nnew, hipMemcpyDeviceToHost));
 }
+
+// the joint posterior of the functions d[0 .. nD) at Xnew, function-major (n = nD * Nnew).  The mean is q(f)'s own (qf_chunk:
+// the same bits as hmogp_predict_f).  G_q = A_q C_q A_q^T follows the mode of the evaluation it is taken from, as qf_chunk does:
+//   default  T = A_q C_q, G_q = T A_q^T                                              (the explicit C_q)
+//   strict   R = A_q Kuu^-1 by the row solves against Luu, T = R L_q, G_q = T T^T - R A_q^T   (svmogp_inf.py:214-218, literally)
+// Every product is the existing GEMM ACCUMULATING into a zeroed target (beta = 1): that pins the general FP64-MFMA kernel whatever the
+// row count, so an entry's k-order -- and with it its bits -- does not depend on which other rows or functions the call has.  Only the
+// lower tiles of G_q are formed; joint_assemble_kernel reads only them.  Every refusal comes before the first device call.
+void hmogp_engine::joint(const double* Xnew, long long Nnew, int nD, const int* d, double* mean, double* cov, int S,
+                         unsigned long long seed, double* F, double* Lout, double* jitter_out, int* rung_out) {
+  const bool sample = S != 0 || F != nullptr;
+  if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to predict from"};
+  if (nD < 1 || !d) throw EngineError{HMOGP_E_INVALID, "joint: nD must be >= 1 and d_index given"};
+  {
+    std::vector<char> seen((size_t)Df, 0);
+    for (int j = 0; j < nD; ++j) {
+      if (d[j] < 0 || d[j] >= Df) throw EngineError{HMOGP_E_INVALID, "joint: a function index is out of range"};
+      if (seen[d[j]]) throw EngineError{HMOGP_E_INVALID, "joint: a function index is repeated"};
+      seen[d[j]] = 1;
+    }
+  }
+  if (Nnew < 0) throw EngineError{HMOGP_E_INVALID, "bad predict arguments"};
+  if (Nnew > HMOGP_JOINT_MAXDIM || (long long)nD * Nnew > HMOGP_JOINT_MAXDIM)
+    throw EngineError{HMOGP_E_INVALID, "joint: nD * Nnew exceeds HMOGP_JOINT_MAXDIM"};
+  if (sample && S < 1) throw EngineError{HMOGP_E_INVALID, "joint: S must be >= 1"};
+  if (Nnew > 0 && (!Xnew || (sample ? !F : (!mean || !cov)))) throw EngineError{HMOGP_E_INVALID, "bad predict arguments"};
+  if (jitter_out) *jitter_out = 0.0;
+  if (rung_out) *rung_out = -1;
+  if (Nnew == 0) return;
+
+  HIP_TRY(hipSetDevice(device));
+  const long long N = Nnew, n = (long long)nD * N, MM = (long long)M * M, sK = N * M, NN = N * N;
+  ensure_workspace(std::min(chunk, N));
+  ensure_strict_workspace();           // (the joint posterior follows the mode of the evaluation it is taken from)
+  const long long ldn = ws_rows;
+  DevBuf dd, dX, dm, dv, jmean, jX, jA, jT, jR, jG, jcov;
+  dd.ensure(sizeof(int) * nD);
+  HIP_TRY(hipMemcpyAsync(dd.p, d, sizeof(int) * nD, hipMemcpyHostToDevice, st));
+  dX.ensure(sizeof(double) * ldn * P), dm.ensure(sizeof(double) * ldn * Df), dv.ensure(sizeof(double) * ldn * Df);
+  jmean.ensure(sizeof(double) * n);
+  for (long long r0 = 0; r0 < N; r0 += ldn) {
+    const long long nn = std::min(ldn, N - r0);
+    qf_chunk(Xnew + r0 * P, nn, dX, dm, dv);
+    launch_joint_gather(dm.d(), Df, dd.as<int>(), nD, N, r0, nn, jmean.d(), st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (dX is reused by the next chunk's upload)
+  }
+  jX.ensure(sizeof(double) * N * P), jA.ensure(sizeof(double) * Q * sK), jT.ensure(sizeof(double) * Q * sK);
+  jG.ensure(sizeof(double) * Q * NN), jcov.ensure(sizeof(double) * n * n);
+  HIP_TRY(hipMemcpyAsync(jX.p, Xnew, sizeof(double) * N * P, hipMemcpyHostToDevice, st));
+  RbfBatch rbt;
+  rbt.nq = Q, rbt.var = dvar.d(), rbt.ell = dell.d(), rbt.sZ = P, rbt.sK = sK;
+  launch_rbf(jX.d(), P, N, P, dZ.d(), Q * P, M, 0.0, 1.0, jA.d(), false, st, nullptr, strict, &rbt);   // A_q: K_uf as qf_chunk rounds it
+  HIP_TRY(hipMemsetAsync(jT.p, 0, sizeof(double) * Q * sK, st));
+  HIP_TRY(hipMemsetAsync(jG.p, 0, sizeof(double) * Q * NN, st));
+  // C_[q] += alpha * A_[q] op(B_[q]), A_ the N x K rows (row-major, lda = M); batched over the latents
+  auto acc = [&](const double* A_, const double* B_, long long sB, int b_kmajor, int b_tri, double* C_, int ldc, long long sC,
+                 int ncols, double alpha, bool lower) {
+    GemmArgs g;
+    g.A = A_, g.lda = M, g.a_kmajor = 0, g.sA = sK;
+    g.B = B_, g.ldb = M, g.b_kmajor = b_kmajor, g.sB = sB, g.b_tri = b_tri;
+    g.C = C_, g.ldc = ldc, g.sC = sC;
+    g.M = (int)N, g.N = ncols, g.K = M;
+    g.nbatch = Q;
+    g.alpha = alpha, g.beta = 1.0;
+    g.lower_only = lower ? 1 : 0;
+    launch_gemm_f64(g, st);
+  };
+  if (strict) {
+    jR.ensure(sizeof(double) * Q * sK);
+    potrs_rows_inplace(jR.d(), sK, Luu.d(), MM, M, N, Q, st, Lsy.d(), jA.d(), rdiag.d(), nullptr, 3, lsym_valid);   // R = A Kuu^-1
+    acc(jR.d(), L.d(), MM, 1, +1, jT.d(), M, sK, M, 1.0, false);               // T = R L_q (L_q lower)
+    acc(jT.d(), jT.d(), sK, 0, 0, jG.d(), (int)N, NN, (int)N, 1.0, true);      // G = T T^T
+    acc(jR.d(), jA.d(), sK, 0, 0, jG.d(), (int)N, NN, (int)N, -1.0, true);     //     - R A^T
+  } else {
+    acc(jA.d(), C.d(), MM, 1, 0, jT.d(), M, sK, M, 1.0, false);                // T = A C_q
+    acc(jT.d(), jA.d(), sK, 0, 0, jG.d(), (int)N, NN, (int)N, 1.0, true);      // G = T A^T
+  }
+  JointArgs ja;
+  ja.P = P, ja.Q = Q, ja.Df = Df, ja.nD = nD, ja.N = N;
+  ja.X = jX.d(), ja.G = jG.d(), ja.W = dW.d(), ja.kap = dkap.d(), ja.var = dvar.d(), ja.ell = dell.d();
+  ja.d = dd.as<int>(), ja.cov = jcov.d();
+  launch_joint_assemble(ja, st);
+  HIP_TRY(hipGetLastError());
+  if (mean) HIP_TRY(hipMemcpyAsync(mean, jmean.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  if (cov) HIP_TRY(hipMemcpyAsync(cov, jcov.p, sizeof(double) * n * n, hipMemcpyDeviceToHost, st));
+  if (!sample) {
+    HIP_TRY(hipStreamSynchronize(st));
+    return;
+  }
+  // L = chol(cov + jitter I) on the ladder hmogp_jitchol_inv climbs (batch of one; the ladder's rung count is bounded), then
+  // F = mean + Z L^T: the normal fill writes the mean into F, the GEMM accumulates onto it (L dense, zeros above the diagonal)
+  std::vector<double> hdiag((size_t)n);
+  HIP_TRY(hipMemcpy2DAsync(hdiag.data(), sizeof(double), jcov.p, sizeof(double) * (n + 1), sizeof(double), (size_t)n,
+                           hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  double dmean = 0.0;
+  for (long long i = 0; i < n; ++i) dmean += hdiag[i];
+  dmean /= (double)n;
+  DevBuf jL, jscr, jinfo, jjit, jZ, jF;
+  jL.ensure(sizeof(double) * n * n), jscr.ensure(sizeof(double) * n * n), jinfo.ensure(sizeof(int)), jjit.ensure(sizeof(double));
+  int r = -2;
+  jitchol_batched(jcov.d(), jL.d(), 1, (int)n, &dmean, &r, jinfo.as<int>(), jjit.d(), jscr.d(), st);
+  if (rung_out) *rung_out = r;
+  if (jitter_out) *jitter_out = r < 0 ? 0.0 : dmean * 1e-6 * std::pow(10.0, r);
+  jZ.ensure(sizeof(double) * S * n), jF.ensure(sizeof(double) * S * n);
+  launch_joint_normal(seed, S, n, jZ.d(), jmean.d(), jF.d(), st);
+  GemmArgs g;
+  g.A = jZ.d(), g.lda = (int)n, g.a_kmajor = 0;
+  g.B = jL.d(), g.ldb = (int)n, g.b_kmajor = 0, g.b_tri = -1;      // op(B)[k][j] = L[j][k]: zero for k > j
+  g.C = jF.d(), g.ldc = (int)n;
+  g.M = S, g.N = (int)n, g.K = (int)n;
+  g.beta = 1.0;
+  launch_gemm_f64(g, st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(F, jF.p, sizeof(double) * S * n, hipMemcpyDeviceToHost, st));
+  if (Lout) HIP_TRY(hipMemcpyAsync(Lout, jL.p, sizeof(double) * n * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+}

@@ -216,6 +216,23 @@ struct PqArgs {
 const char* predq_refusal(int lik);   // nullptr for the six families, else the reason the family is refused
 void launch_predictive_cdf(const PqArgs& a, hipStream_t s);
 void launch_predictive_quantile(const PqArgs& a, hipStream_t s);
+// Joint posterior covariance at new inputs (joint.hip): cov[(j, i), (j', i')] = sum_q (w_jq w_j'q + kap_jq [j == j']) k_q(x_i, x_i')
+// + w_jq w_j'q G_q[max(i, i'), min(i, i')] for every pair of the nD functions d[j], one 64 x 64 tile of (i, i') per block; lower tiles
+// computed, their mirror images written from the same registers.  G: [Q][N][N] (only its lower triangle is read); W, kap: [Q][Df];
+// var, ell: [Q]; X: [N][P]; cov: [nD N][nD N].  Every pointer is device memory.
+struct JointArgs {
+  int P = 1, Q = 1, Df = 1, nD = 1;
+  long long N = 0;
+  const double *X = nullptr, *G = nullptr, *W = nullptr, *kap = nullptr, *var = nullptr, *ell = nullptr;
+  const int* d = nullptr;          // [nD]
+  double* cov = nullptr;
+};
+void launch_joint_assemble(const JointArgs& a, hipStream_t s);
+// Z[s][i] = z0 of normal_pair(seed, row i, sample s, pair 0) for s < S, i < n; with F (and mean [n]): F[s][i] = mean[i] beside it
+void launch_joint_normal(unsigned long long seed, int S, long long n, double* Z, const double* mean, double* F, hipStream_t s);
+// mean[j * N + i] = m[i * Df + d[j]]: the joint vector's function-major mean out of q(f)'s [N][Df] rows (i0: first row of the chunk)
+void launch_joint_gather(const double* m, int Df, const int* d, int nD, long long N, long long i0, long long nrows, double* mean,
+                         hipStream_t s);
 // Y[n] ~ p(y | F[n]): the reference's `<likelihood>.samples`, one draw per row, counter-based generator
 void launch_sample(int lik, int J, double param, long long N, unsigned long long seed, const double* F, double* Y,
                    hipStream_t s);

@@ -376,6 +376,42 @@ class Engine(object):
         check(lib.hmogp_predict_f(self._h, _p(Xnew), Xnew.shape[0], _p(m), _p(v)), self._h)
         return m, v
 
+    def _joint_functions(self, functions):
+        d = np.arange(self.Df) if functions is None else np.asarray(functions).reshape(-1)
+        if d.size and not np.issubdtype(d.dtype, np.integer):
+            raise _lib.InvalidArgument("functions must be integer indices")
+        return np.ascontiguousarray(d, dtype=np.int32)
+
+    def predict_f_joint(self, Xnew, functions=None):
+        """The joint posterior of the functions `functions` (None: all Df) at Xnew: (mean (nD, N), cov (nD, N, nD, N)),
+        cov exactly symmetric as an (nD N) x (nD N) matrix; nD * N <= _lib.JOINT_MAXDIM."""
+        Xnew = _f64(Xnew).reshape(-1, self.P)
+        d = self._joint_functions(functions)
+        N, nD = Xnew.shape[0], d.shape[0]
+        mean = np.zeros((nD, N))
+        cov = np.zeros((nD * N, nD * N)) if nD * N <= _lib.JOINT_MAXDIM else np.zeros((0, 0))     # (beyond the limit the call is refused)
+        check(lib.hmogp_predict_f_joint(self._h, _p(Xnew), N, nD, d.ctypes.data_as(_lib.c_int32_p), _p(mean), _p(cov)), self._h)
+        return mean, cov.reshape(nD, N, nD, N)
+
+    def sample_f_joint(self, Xnew, functions=None, size=1, seed=0, return_factor=False):
+        """`size` joint draws F[s] = mean + L z_s of the same Gaussian: (size, nD, N).  L = chol(cov + jitter I) on the ladder of
+        `jitchol_inv`; z_s[i] is the counter-based normal at (seed, row i, sample s), so draw s does not depend on `size`.
+        return_factor=True: (F, dict(mean (nD, N), L (nD N, nD N), jitter, rung)) -- rung -1 / jitter 0: the plain factorisation."""
+        Xnew = _f64(Xnew).reshape(-1, self.P)
+        d = self._joint_functions(functions)
+        N, nD, S = Xnew.shape[0], d.shape[0], int(size)
+        n = nD * N
+        ok = n <= _lib.JOINT_MAXDIM and S >= 1
+        F = np.zeros((S, nD, N)) if ok else np.zeros((1, 0, 0))
+        mean = np.zeros((nD, N))
+        L = np.zeros((n, n)) if (return_factor and ok) else None
+        jit, rung = C.c_double(0.0), C.c_int32(-1)
+        check(lib.hmogp_sample_f_joint(self._h, _p(Xnew), N, nD, d.ctypes.data_as(_lib.c_int32_p), S, int(seed) & (2 ** 64 - 1), _p(F),
+                                       _p(mean), _p(L) if L is not None else None, C.byref(jit), C.byref(rung)), self._h)
+        if return_factor:
+            return F, dict(mean=mean, L=L, jitter=float(jit.value), rung=int(rung.value))
+        return F
+
     # ------------------------------------------------------------------------------------------ resident q(u)
     def qu_load(self, m_u, L_flat):
         m_u, L_flat = _f64(m_u).reshape(self.M, self.Q), _f64(L_flat).reshape(self.Mtri, self.Q)

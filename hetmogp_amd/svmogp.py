@@ -830,10 +830,45 @@ class SVMOGP(object):
         m, v = self._engine.predict_f(np.asarray(Xnew, dtype=float).reshape(-1, self.Xdim))
         return m[:, d:d + 1], np.abs(v[:, d:d + 1])
 
-    def predict_f(self, Xnew):
-        """q(f_d) at Xnew for every function d: (mean [N, Df], variance [N, Df])."""
+    def predict_f(self, Xnew, full_cov=False, functions=None):
+        """q(f_d) at Xnew for every function d: (mean [N, Df], variance [N, Df]).  full_cov=True (GPy's `predict(full_cov=True)`;
+        DESIGN 9r): the JOINT posterior of the functions `functions` (None: all) -- (mean [N, nD], cov [nD, N, nD, N]), cov[j, i, j', i'] =
+        cov(f_dj(x_i), f_dj'(x_i')), exactly symmetric, its diagonal the variance above before any abs; nD * N <= 8192."""
         self._refresh()
-        return self._engine.predict_f(np.asarray(Xnew, dtype=float).reshape(-1, self.Xdim))
+        Xnew = np.asarray(Xnew, dtype=float).reshape(-1, self.Xdim)
+        if not full_cov:
+            if functions is not None:
+                raise ValueError("predict_f: `functions` selects the functions of the joint posterior (full_cov=True)")
+            return self._engine.predict_f(Xnew)
+        mean, cov = self._engine.predict_f_joint(Xnew, functions)
+        return np.ascontiguousarray(mean.T), cov
+
+    def _joint_seed(self, seed):
+        if seed is None:       # (as `_Lik.samples`: one draw from NumPy's GLOBAL generator)
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        return int(seed)
+
+    def posterior_samples_f(self, Xnew, size=10, functions=None, seed=None):
+        """`size` sample paths of the functions `functions` (None: all) at Xnew, drawn JOINTLY over functions and inputs from the
+        posterior of `predict_f(full_cov=True)` (GPy's `posterior_samples_f`): (size, N, nD).  Draw s depends on (seed, s)
+        only, not on `size`; seed=None draws the seed from NumPy's global generator."""
+        self._refresh()
+        F = self._engine.sample_f_joint(np.asarray(Xnew, dtype=float).reshape(-1, self.Xdim), functions, size=size,
+                                        seed=self._joint_seed(seed))
+        return np.ascontiguousarray(np.transpose(F, (0, 2, 1)))
+
+    def posterior_samples(self, Xnew, task, size=10, seed=None):
+        """`size` draws of task `task`'s output at Xnew (GPy's `posterior_samples`): the task's functions are drawn jointly
+        (`posterior_samples_f`), each draw is then pushed through the likelihood's sampler on the device (`hmogp_sample`, keyed by
+        seed + 1 and the row s N + i).  (size, N); (size, N, K) for Dirichlet."""
+        t = int(task)
+        lik = self.likelihood.likelihoods_list[t]
+        cols = [d for d in range(self.num_output_funcs) if self.Y_metadata["function_index"].flatten()[d] == t]
+        seed = self._joint_seed(seed)
+        F = self.posterior_samples_f(Xnew, size=size, functions=cols, seed=seed)
+        S, N, J = F.shape
+        Y = np.asarray(lik.samples(F.reshape(S * N, J), seed=seed + 1))        # one launch: row s N + i is draw s at input i
+        return Y.reshape(S, N, -1) if lik.name == "Dirichlet" else Y.reshape(S, N)
 
     def _raw_predict_f(self, Xnew, output_function_ind=None, kern_list=None):
         """svmogp.py:255-278, the route the reference's `predictive` / `negative_log_predictive` take: q(f_d) at the TRAINING

@@ -544,6 +544,28 @@ int hmogp_predict_cdf(hmogp_handle h, int32_t t, const double* Xnew, const doubl
 int hmogp_predict_quantile(hmogp_handle h, int32_t t, const double* Xnew, int64_t Nnew, int32_t nP, const double* p /* [nP] */,
                            int32_t gh_T, double* q /* [Nnew, nP] */);
 
+/* The JOINT posterior at new inputs: the Gaussian over f = (f_{d_1}(x_1..x_N), ..., f_{d_nD}(x_1..x_N)), function-major,
+ * n = nD * Nnew, for nD distinct function indices d_index[j] in 0 .. Df-1, from the parameters of the last evaluation and in its
+ * mode (default: through the explicit C_q; strict: through solves against Luu), small or regular model:
+ *   mean[j, i]            = hmogp_predict_f's m[i, d_j]
+ *   cov[(j, i), (j', i')] = sum_q (W_q[d_j] W_q[d_j'] + kappa_q[d_j] [j == j']) k_q(x_i, x_i') + W_q[d_j] W_q[d_j'] G_q[i, i'],
+ *   G_q = A_q C_q A_q^T,  A_q = k_q(Xnew, Z_q),  C_q = Kuu^-1 S_q Kuu^-1 - Kuu^-1
+ * cov [n, n] is written exactly symmetric (lower tiles computed, mirrored bit for bit); its diagonal is hmogp_predict_f's v before
+ * any abs.  k_q(x_i, x_i') takes GPy's rounding order, so its diagonal is exactly the variance.
+ * hmogp_sample_f_joint: F[s] = mean + L z_s for s < S, L the lower Cholesky factor of cov + jitter I on the ladder of
+ * hmogp_jitchol_inv (first try without jitter: *rung_out = -1 and *jitter_out = 0; else rung k = 0 .. 4 and jitter = mean(diag cov)
+ * 1e-6 10^k; HMOGP_E_NOT_PD beyond), z_s[i] = z0 of the counter-based normal generator at (seed, row i, sample s, pair 0) -- so
+ * draw s does not depend on S.  F is [S, n]; mean [n], L [n, n] (dense, zeros above the diagonal), jitter_out, rung_out may be NULL.
+ * HMOGP_E_STATE before the first evaluation; HMOGP_E_INVALID for nD < 1, an index out of range or repeated, n >
+ * HMOGP_JOINT_MAXDIM, S < 1, or a NULL required pointer with Nnew > 0 -- every refusal before anything is launched.  Nnew = 0
+ * returns at once.  New symbols only: ABI version 8 stays.                                                                       */
+#define HMOGP_JOINT_MAXDIM 8192
+int hmogp_predict_f_joint(hmogp_handle h, const double* Xnew, int64_t Nnew, int32_t nD, const int32_t* d_index /* [nD] */,
+                          double* mean /* [nD, Nnew] */, double* cov /* [nD Nnew, nD Nnew] */);
+int hmogp_sample_f_joint(hmogp_handle h, const double* Xnew, int64_t Nnew, int32_t nD, const int32_t* d_index /* [nD] */, int32_t S,
+                         uint64_t seed, double* F /* [S, nD, Nnew] */, double* mean /* [nD, Nnew] or NULL */,
+                         double* L /* [n, n] or NULL */, double* jitter_out /* or NULL */, int32_t* rung_out /* or NULL */);
+
 /* Data generation on the device: one draw Y[n] ~ p(y | F[n, :]) per row with the link functions and clips of the
  * reference's `<likelihood>.samples` (het_likelihood.py:72-83 -> e.g. gamma.py:43-50, categorical.py:65-75; labels of
  * Categorical are 1..K).  Counter-based generator keyed by (seed, row): reproducible, but a different stream than

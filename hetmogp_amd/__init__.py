@@ -9,3 +9,4 @@ from .svmogp import SVMOGP, HetMOGP  # noqa: F401
 from .likelihoods import (HetLikelihood, Gaussian, Bernoulli, HetGaussian, Categorical, Poisson, Exponential, Gamma,  # noqa: F401
                           Beta, Student, Ordinal, Dirichlet, NegBinomial, Weibull, Binomial, BetaBinomial, ZIPoisson)
 from .util import vem_algorithm, latent_functions_prior, random_W_kappas, LCM  # noqa: F401
+from .inducing import select_inducing  # noqa: F401

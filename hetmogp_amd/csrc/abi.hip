@@ -1,6 +1,7 @@
 // abi.hip -- the C ABI of include/hetmogp_hip.h: argument checks, error mapping (guarded), the engine entry points and the
 // stand-alone building blocks.  Split out of engine.hip in round 6 (no behaviour change).
 #include "engine_impl.h"
+#include "zsel.h"
 
 // =================================================================================================== C ABI
 namespace {
@@ -407,6 +408,16 @@ int hmogp_rbf_cross_cov_ex(int32_t device, const double* X, int64_t N, const dou
     launch_rbf(dX.d(), P, N, P, dZ.d(), P, M, variance, lengthscale, dK.d(), false, nullptr, nullptr, exact != 0);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(K, dK.p, sizeof(double) * N * M, hipMemcpyDeviceToHost));
+  });
+}
+
+int hmogp_select_inducing(int32_t device, int64_t N, int32_t P, const double* X, int32_t Q, const double* variance,
+                          const double* lengthscale, int32_t Mmax, double tol, int32_t n_forced, const int64_t* forced, int64_t* pivots,
+                          double* Z, double* dpiv, double* trace, double* L, double* d, int32_t* Mout) {
+  return guarded(nullptr, [&] {
+    select_inducing_check(N, P, X, Q, variance, lengthscale, Mmax, tol, n_forced, forced, pivots, Z, dpiv, trace, Mout);   // on the host, first
+    need_device(device);
+    select_inducing_run(N, P, X, Q, variance, lengthscale, Mmax, tol, n_forced, forced, pivots, Z, dpiv, trace, L, d, Mout);
   });
 }
 

@@ -752,3 +752,34 @@ def sample(name, F, seed=0, device=None, **kw):
     Y = np.zeros((F.shape[0], 1 if name in _TWO_COLUMN_Y else lik_dim_y(name, **kw)))
     check(lib.hmogp_sample(device, LIK_IDS[name], lik_param(name, **kw), F.shape[0], int(seed) & (2 ** 64 - 1), _p(F), _p(Y)))
     return Y
+
+
+def select_inducing_rows(X, variance, lengthscale, Mmax, tol=0.0, forced=None, return_factor=False, device=None):
+    """Inducing inputs chosen from the rows of X by greedy conditional variance = pivoted incomplete Cholesky of K_ff under the sum
+    kernel k = sum_q variance[q] exp(-r_q^2 / 2) (`hmogp_select_inducing`; DESIGN 9s).  X (N, P); variance, lengthscale: Q values each;
+    `forced`: rows that are picked first, in that order.  Returns a dict: Mout, pivots (Mout,) int64, Z (Mout, P), dpiv (Mout,) = d at
+    each pick (its root is the Cholesky diagonal of K_uu in pick order), trace (Mout + 1,) = tr(K_ff - Q_ff) before each pick and after
+    the last; with return_factor also L (N, Mmax) (columns at Mout and beyond are zero) and the final d (N,)."""
+    device = _resolve_device(device)
+    X = _f64(X)
+    X = X.reshape(X.shape[0], -1) if X.ndim != 2 else X
+    N, P = X.shape
+    var, ell = _f64(np.atleast_1d(variance)).ravel(), _f64(np.atleast_1d(lengthscale)).ravel()
+    if var.shape != ell.shape:
+        raise _lib.InvalidArgument("select_inducing_rows: variance and lengthscale must have one entry per kernel each")
+    Mmax = int(Mmax)
+    fo = np.zeros(0, dtype=np.int64) if forced is None else np.ascontiguousarray(np.ravel(forced), dtype=np.int64)
+    Ma = max(Mmax, 1)
+    pivots, Z, dpiv, trace = np.zeros(Ma, dtype=np.int64), np.zeros((Ma, max(P, 1))), np.zeros(Ma), np.zeros(Ma + 1)
+    L = np.zeros((max(N, 1), Ma)) if return_factor else None
+    d = np.zeros(max(N, 1)) if return_factor else None
+    Mout = C.c_int32(0)
+    check(lib.hmogp_select_inducing(device, N, P, _p(X), var.shape[0], _p(var), _p(ell), Mmax, float(tol), fo.shape[0],
+                                    fo.ctypes.data_as(_lib.c_int64_p) if fo.shape[0] else None, pivots.ctypes.data_as(_lib.c_int64_p),
+                                    _p(Z), _p(dpiv), _p(trace), _p(L) if return_factor else None, _p(d) if return_factor else None,
+                                    C.byref(Mout)))
+    M = int(Mout.value)
+    out = dict(Mout=M, pivots=pivots[:M].copy(), Z=Z[:M].copy(), dpiv=dpiv[:M].copy(), trace=trace[:M + 1].copy())
+    if return_factor:
+        out.update(L=L, d=d)
+    return out

@@ -566,6 +566,32 @@ int hmogp_sample_f_joint(hmogp_handle h, const double* Xnew, int64_t Nnew, int32
                          uint64_t seed, double* F /* [S, nD, Nnew] */, double* mean /* [nD, Nnew] or NULL */,
                          double* L /* [n, n] or NULL */, double* jitter_out /* or NULL */, int32_t* rung_out /* or NULL */);
 
+/* Inducing inputs chosen from the data by greedy conditional variance = pivoted incomplete Cholesky of K_ff (Burt,
+ * Rasmussen & van der Wilk 2020).  Stateless: no engine handle.  X [N, P] are the pooled rows, 1 <= P <= 4; the kernel of the
+ * selection is k = sum_q variance[q] exp(-r_q^2 / 2) over the Q <= 8 RBF kernels (one Z serves all latents): r_q^2 in GPy's rounding
+ * order with no contraction (what K_uu is built with), the sum over q from left to right, k0 = sum_q variance[q] summed the same way.
+ *   d_i = k0 for all rows; then for j = 0 .. Mmax-1:
+ *   1. p_j = forced[j] for j < n_forced, else the row with the largest d_i, ties to the SMALLEST index (so the first free pick is row 0);
+ *   2. stop with *Mout = j if d_{p_j} <= max(tol, HMOGP_ZSEL_FLOOR) k0 -- forced picks too (below the floor d is rounding noise, and
+ *      dividing by its root would fill a column with garbage);
+ *   3. c_i = (k(x_i, x_{p_j}) - sum_{l<j} L_il L_{p_j l}) / sqrt(d_{p_j}), the sum ONE chain over l = 0, 1, .., j-1 per row (a row's
+ *      result does not depend on the other rows or the grid);  L_ij = c_i,  d_i = max(d_i - c_i^2, 0),  d_{p_j} = 0 explicitly.
+ * Out: *Mout; pivots[0 .. Mout); Z [Mout, P] = the pivots' rows; dpiv[j] = d_{p_j} at the time of the pick (its square root is the
+ * Cholesky diagonal of K_uu in pick order); trace[0 .. Mout] = sum_i d_i before pick j, trace[Mout] the value after the last pick
+ * (= tr(K_ff - Q_ff)); optionally L [N, Mmax] (columns at Mout and beyond are zero) and the final d [N].  The arrays are sized by Mmax
+ * (pivots, dpiv [Mmax]; Z [Mmax, P]; trace [Mmax + 1]); entries beyond Mout come back as -1 (pivots) or 0.
+ * HMOGP_E_INVALID, with a message that names the argument and before the device is touched, for N < 1, P outside 1..4, Q outside 1..8,
+ * Mmax < 1, a non-finite entry of X, a variance or lengthscale that is not finite and > 0, tol negative or NaN, n_forced outside
+ * 0..Mmax, a forced index out of range or repeated, or a NULL pointer (forced with n_forced = 0, L and d excepted).  Then
+ * HMOGP_E_NO_DEVICE without a device, and HMOGP_E_INVALID (the message gives the bytes needed) if the factor's 8 N Mmax bytes plus the
+ * row arrays exceed the device's free memory -- asked before any allocation.  New symbol only: ABI version 8 stays.                  */
+#define HMOGP_ZSEL_FLOOR 9.094947017729282e-13 /* 2^-40 */
+int hmogp_select_inducing(int32_t device, int64_t N, int32_t P, const double* X /* [N, P] */, int32_t Q, const double* variance /* [Q] */,
+                          const double* lengthscale /* [Q] */, int32_t Mmax, double tol, int32_t n_forced,
+                          const int64_t* forced /* [n_forced] or NULL */, int64_t* pivots /* [Mmax] */, double* Z /* [Mmax, P] */,
+                          double* dpiv /* [Mmax] */, double* trace /* [Mmax + 1] */, double* L /* [N, Mmax] or NULL */,
+                          double* d /* [N] or NULL */, int32_t* Mout);
+
 /* Data generation on the device: one draw Y[n] ~ p(y | F[n, :]) per row with the link functions and clips of the
  * reference's `<likelihood>.samples` (het_likelihood.py:72-83 -> e.g. gamma.py:43-50, categorical.py:65-75; labels of
  * Categorical are 1..K).  Counter-based generator keyed by (seed, row): reproducible, but a different stream than

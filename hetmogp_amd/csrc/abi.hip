@@ -44,8 +44,25 @@ void upload_y(int lik_id, double lik_param, const double* y, long long N, DevBuf
 
 // Binomial, Beta-Binomial: the trial count n* is refused on the host, before the device is asked for (the same answer with or without one)
 void check_trials_first(int lik_id, double lik_param) {
-  if (lik_id == HMOGP_LIK_BINOMIAL || lik_id == HMOGP_LIK_BETABINOMIAL) check_lik_param(lik_id, lik_param);
+  if (lik_has_trials(lik_id)) check_lik_param(lik_id, lik_param);
 }
+
+// What every stand-alone building block does once its host-side refusals are through, in this order: the device, the Gaussian default
+// sigma (hmogp_log_predictive alone does not apply it), the functions per row, the parameter check.  Returns the functions per row.
+int block_begin(int device, int lik_id, double& lik_param, bool gaussian_default = true) {
+  need_device(device);
+  if (gaussian_default && lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
+  const int J = lik_dimf(lik_id, lik_param);
+  check_lik_param(lik_id, lik_param);
+  return J;
+}
+
+// `count` doubles of the host -> a device buffer of that size, and back
+void to_device(DevBuf& d, const double* src, size_t count) {
+  d.ensure(sizeof(double) * count);
+  HIP_TRY(hipMemcpy(d.p, src, sizeof(double) * count, hipMemcpyHostToDevice));
+}
+void to_host(double* dst, const DevBuf& d, size_t count) { HIP_TRY(hipMemcpy(dst, d.p, sizeof(double) * count, hipMemcpyDeviceToHost)); }
 
 // Zero-inflated Poisson: the counts are refused on the host, before the device is asked for (the same answer with or without one)
 void check_counts_first(int lik_id, int64_t N, const double* y) {
@@ -53,67 +70,6 @@ void check_counts_first(int lik_id, int64_t N, const double* y) {
 }
 
 }  // namespace
-
-namespace hmogp_detail {
-// y [N] of a building block -> device.  Ordinal: the labels are checked and replaced by the rows' lower, then upper cut points
-// ([2][N], what launch_var_exp / launch_log_predictive read), so that the device code is the engine's.  Dirichlet: y is [N][K]; it is
-// checked and replaced by log y_k as [K][N], the engine's layout.  Negative Binomial, zero-inflated Poisson: the counts are checked and
-// uploaded as they are.
-// Weibull: y is [N][2] = (y, delta); it is checked and replaced by (log y, delta) as [2][N], the engine's layout.
-// Binomial, Beta-Binomial: y is [N][2] = (k, n); it is checked and replaced by (k, n, lc) as [3][N].
-// `tb`: the Ordinal table to cut by instead of the registry entry `lik_param` names (a task's private table).
-void upload_y_image(int lik_id, double lik_param, const OrdinalTable* tb, const double* y, long long N, DevBuf& dy) {
-  if (lik_id == HMOGP_LIK_WEIBULL) {
-    std::vector<double> img(2 * (size_t)N);
-    weibull_check_rows(y, N, img.data());
-    dy.ensure(sizeof(double) * 2 * N);
-    HIP_TRY(hipMemcpy(dy.p, img.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
-    return;
-  }
-  if (lik_id == HMOGP_LIK_BINOMIAL || lik_id == HMOGP_LIK_BETABINOMIAL) {
-    std::vector<double> img(3 * (size_t)N);
-    binomial_check_rows(lik_id, y, N, img.data());
-    dy.ensure(sizeof(double) * 3 * N);
-    HIP_TRY(hipMemcpy(dy.p, img.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
-    return;
-  }
-  if (lik_id == HMOGP_LIK_DIRICHLET) {
-    const int K = (int)lik_param;
-    std::vector<double> ly((size_t)K * N);
-    dirichlet_log_rows(K, y, N, ly.data());
-    dy.ensure(sizeof(double) * K * N);
-    HIP_TRY(hipMemcpy(dy.p, ly.data(), sizeof(double) * K * N, hipMemcpyHostToDevice));
-    return;
-  }
-  if (lik_id == HMOGP_LIK_NEGBINOMIAL) negbinomial_check_rows(y, N);
-  if (lik_id == HMOGP_LIK_ZIPOISSON) zipoisson_check_rows(y, N);
-  if (lik_id != HMOGP_LIK_ORDINAL) {
-    dy.ensure(sizeof(double) * N);
-    HIP_TRY(hipMemcpy(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice));
-    return;
-  }
-  std::vector<double> cuts(2 * (size_t)N);
-  ordinal_row_cuts(tb ? *tb : ordinal_table(lik_param), y, N, cuts.data(), cuts.data() + N);
-  dy.ensure(sizeof(double) * 2 * N);
-  HIP_TRY(hipMemcpy(dy.p, cuts.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
-}
-void upload_y_cdf(int lik_id, double lik_param, const OrdinalTable* tb, const double* y, long long N, DevBuf& dy) {
-  if (lik_id != HMOGP_LIK_WEIBULL) {
-    upload_y_image(lik_id, lik_param, tb, y, N, dy);
-    return;
-  }
-  std::vector<double> ly((size_t)N);
-  for (long long n = 0; n < N; ++n) ly[n] = y[n] > 0.0 ? std::log(y[n]) : (y[n] <= 0.0 ? -INFINITY : y[n]);
-  dy.ensure(sizeof(double) * N);
-  HIP_TRY(hipMemcpy(dy.p, ly.data(), sizeof(double) * N, hipMemcpyHostToDevice));
-}
-
-int predq_nodes(int lik_id, int gh_T) {
-  if (const char* why = predq_refusal(lik_id)) throw EngineError{HMOGP_E_INVALID, why};
-  if (gh_T != 0 && gh_T != 10 && gh_T != 20) throw EngineError{HMOGP_E_INVALID, "gh_T must be 0, 10 or 20"};
-  return gh_T == 0 ? 20 : gh_T;
-}
-}  // namespace hmogp_detail
 
 extern "C" {
 
@@ -520,23 +476,17 @@ int hmogp_var_exp_ex(int32_t device, int32_t lik_id, double lik_param, uint32_t 
   return guarded(nullptr, [&] {
     check_trials_first(lik_id, lik_param);
     check_counts_first(lik_id, N, y);
-    need_device(device);
-    if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
-    const int J = lik_dimf(lik_id, lik_param);
-    check_lik_param(lik_id, lik_param);
+    const int J = block_begin(device, lik_id, lik_param);
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !y || !m || !v || !ve || !dm || !dv)
       throw EngineError{HMOGP_E_INVALID, "bad arguments"};
     DevBuf dy, dmm, dvv, dve, ddm, ddv;
     upload_y(lik_id, lik_param, y, N, dy);
     dve.ensure(sizeof(double) * N);
-    for (DevBuf* b : {&dmm, &dvv, &ddm, &ddv}) b->ensure(sizeof(double) * N * J);
-    HIP_TRY(hipMemcpy(dmm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dvv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
+    for (DevBuf* b : {&ddm, &ddv}) b->ensure(sizeof(double) * N * J);
+    to_device(dmm, m, (size_t)N * J), to_device(dvv, v, (size_t)N * J);
     launch_var_exp(lik_id, J, lik_param, N, dy.d(), dmm.d(), dvv.d(), dve.d(), ddm.d(), ddv.d(), nullptr, quirks);
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(ve, dve.p, sizeof(double) * N, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dm, ddm.p, sizeof(double) * N * J, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dv, ddv.p, sizeof(double) * N * J, hipMemcpyDeviceToHost));
+    to_host(ve, dve, N), to_host(dm, ddm, (size_t)N * J), to_host(dv, ddv, (size_t)N * J);
   });
 }
 
@@ -544,21 +494,17 @@ int hmogp_var_exp_dparam(int32_t device, int32_t lik_id, double lik_param, int64
                          const double* v, double* out) {
   return guarded(nullptr, [&] {
     check_trials_first(lik_id, lik_param);
-    need_device(device);
-    if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
-    const int J = lik_dimf(lik_id, lik_param);
-    check_lik_param(lik_id, lik_param);
+    const int J = block_begin(device, lik_id, lik_param);
     const int Cn = lik_dparam_cols(lik_id);
     if (Cn == 0) throw EngineError{HMOGP_E_INVALID, "hmogp_var_exp_dparam: this likelihood has no parameters of its own"};
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !y || !m || !v || !out) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
     DevBuf dy, dmm, dvv, dout;
     upload_y(lik_id, lik_param, y, N, dy);
-    dmm.ensure(sizeof(double) * N * J), dvv.ensure(sizeof(double) * N * J), dout.ensure(sizeof(double) * N * Cn);
-    HIP_TRY(hipMemcpy(dmm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dvv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
+    dout.ensure(sizeof(double) * N * Cn);
+    to_device(dmm, m, (size_t)N * J), to_device(dvv, v, (size_t)N * J);
     launch_var_exp_dparam(lik_id, lik_param, N, dy.d(), dmm.d(), dvv.d(), dout.d(), nullptr);
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, dout.p, sizeof(double) * N * Cn, hipMemcpyDeviceToHost));
+    to_host(out, dout, (size_t)N * Cn);
   });
 }
 
@@ -590,23 +536,17 @@ int hmogp_predictive(int32_t device, int32_t lik_id, double lik_param, int32_t g
                      const double* v, double* mean, double* var) {
   return guarded(nullptr, [&] {
     check_trials_first(lik_id, lik_param);
-    need_device(device);
-    if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
-    const int J = lik_dimf(lik_id, lik_param);
-    check_lik_param(lik_id, lik_param);
+    const int J = block_begin(device, lik_id, lik_param);
     const int Jp = (lik_id == HMOGP_LIK_CATEGORICAL || lik_id == HMOGP_LIK_DIRICHLET) ? J : 1;  // dim_p of get_metadata()
     if (gh_T == 0) gh_T = (lik_id == HMOGP_LIK_CATEGORICAL) ? 10 : 20;
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !m || !v || !mean || !var || (gh_T != 10 && gh_T != 20))
       throw EngineError{HMOGP_E_INVALID, "bad arguments"};
     DevBuf dm, dv, om, ov;
-    dm.ensure(sizeof(double) * N * J), dv.ensure(sizeof(double) * N * J);
     om.ensure(sizeof(double) * N * Jp), ov.ensure(sizeof(double) * N * Jp);
-    HIP_TRY(hipMemcpy(dm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
+    to_device(dm, m, (size_t)N * J), to_device(dv, v, (size_t)N * J);
     launch_predictive(lik_id, J, Jp, lik_param, gh_T, N, dm.d(), dv.d(), om.d(), ov.d(), nullptr);
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(mean, om.p, sizeof(double) * N * Jp, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(var, ov.p, sizeof(double) * N * Jp, hipMemcpyDeviceToHost));
+    to_host(mean, om, (size_t)N * Jp), to_host(var, ov, (size_t)N * Jp);
   });
 }
 
@@ -615,9 +555,7 @@ int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64
   return guarded(nullptr, [&] {
     check_trials_first(lik_id, lik_param);
     check_counts_first(lik_id, N, y);
-    need_device(device);
-    const int J = lik_dimf(lik_id, lik_param);
-    check_lik_param(lik_id, lik_param);
+    const int J = block_begin(device, lik_id, lik_param, /*gaussian_default=*/false);
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || num_samples < 1 || !y || !m || !v || !log_pred)
       throw EngineError{HMOGP_E_INVALID, "bad arguments"};
     if (lik_id == HMOGP_LIK_GAMMA || lik_id == HMOGP_LIK_BETA)
@@ -625,22 +563,11 @@ int hmogp_log_predictive(int32_t device, int32_t lik_id, double lik_param, int64
     DevBuf dy, dm, dv, dout;
     upload_y(lik_id, lik_param, y, N, dy);
     dout.ensure(sizeof(double) * N);
-    dm.ensure(sizeof(double) * N * J), dv.ensure(sizeof(double) * N * J);
-    HIP_TRY(hipMemcpy(dm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
+    to_device(dm, m, (size_t)N * J), to_device(dv, v, (size_t)N * J);
     launch_log_predictive(lik_id, J, lik_param, N, num_samples, seed, dy.d(), dm.d(), dv.d(), dout.d(), nullptr);
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(log_pred, dout.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+    to_host(log_pred, dout, N);
   });
-}
-
-// nodes per dimension of the deterministic rule: 0 = the default, 20, but 10 for Categorical and Dirichlet, which take no other
-static int lpd_nodes(int lik_id, int gh_T) {
-  const bool tensor10 = lik_id == HMOGP_LIK_CATEGORICAL || lik_id == HMOGP_LIK_DIRICHLET;
-  if (gh_T == 0) return tensor10 ? 10 : 20;
-  if (tensor10 ? gh_T != 10 : (gh_T != 10 && gh_T != 20))
-    throw EngineError{HMOGP_E_INVALID, tensor10 ? "gh_T must be 0 or 10 for Categorical / Dirichlet" : "gh_T must be 0, 10 or 20"};
-  return gh_T;
 }
 
 int hmogp_log_predictive_gh(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, const double* y,
@@ -648,19 +575,15 @@ int hmogp_log_predictive_gh(int32_t device, int32_t lik_id, double lik_param, in
   return guarded(nullptr, [&] {
     check_trials_first(lik_id, lik_param);
     check_counts_first(lik_id, N, y);
-    need_device(device);
-    if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
-    const int J = lik_dimf(lik_id, lik_param);
-    check_lik_param(lik_id, lik_param);
+    const int J = block_begin(device, lik_id, lik_param);
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !y || !m || !v || !lpd) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
     LpdArgs a;
     a.T = lpd_nodes(lik_id, gh_T);
     DevBuf dy, dm, dv, dl, de;
     upload_y(lik_id, lik_param, y, N, dy);
-    dm.ensure(sizeof(double) * N * J), dv.ensure(sizeof(double) * N * J), dl.ensure(sizeof(double) * N);
+    dl.ensure(sizeof(double) * N);
     if (ess) de.ensure(sizeof(double) * N);
-    HIP_TRY(hipMemcpy(dm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
+    to_device(dm, m, (size_t)N * J), to_device(dv, v, (size_t)N * J);
     a.lik = lik_id, a.J = J, a.N = N;
     a.param = lik_id == HMOGP_LIK_ORDINAL ? ordinal_table(lik_param).sigma : lik_param;
     a.y = dy.d(), a.ldy = N, a.m = dm.d(), a.v = dv.d(), a.ldf = J;
@@ -668,8 +591,8 @@ int hmogp_log_predictive_gh(int32_t device, int32_t lik_id, double lik_param, in
     launch_log_predictive_gh(a, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(lpd, dl.p, sizeof(double) * N, hipMemcpyDeviceToHost));
-    if (ess) HIP_TRY(hipMemcpy(ess, de.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+    to_host(lpd, dl, N);
+    if (ess) to_host(ess, de, N);
   });
 }
 
@@ -699,9 +622,7 @@ static void predq_rows(int32_t device, int32_t lik_id, double lik_param, int32_t
   DevBuf dy, dm, dv, d1, d2;
   const OrdinalTable* tb = lik_id == HMOGP_LIK_ORDINAL ? &ordinal_table(lik_param) : nullptr;
   if (!quant) upload_y_cdf(lik_id, lik_param, nullptr, y, N, dy);
-  dm.ensure(sizeof(double) * N * J), dv.ensure(sizeof(double) * N * J);
-  HIP_TRY(hipMemcpy(dm.p, m, sizeof(double) * N * J, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dv.p, v, sizeof(double) * N * J, hipMemcpyHostToDevice));
+  to_device(dm, m, (size_t)N * J), to_device(dv, v, (size_t)N * J);
   a.lik = lik_id, a.N = N, a.param = tb ? tb->sigma : lik_param, a.table = tb;
   a.m = dm.d(), a.v = dv.d(), a.ldf = J;
   if (quant) {
@@ -717,9 +638,9 @@ static void predq_rows(int32_t device, int32_t lik_id, double lik_param, int32_t
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  if (quant) HIP_TRY(hipMemcpy(q, d1.p, sizeof(double) * N * nP, hipMemcpyDeviceToHost));
-  if (!quant && cdf) HIP_TRY(hipMemcpy(cdf, d1.p, sizeof(double) * N, hipMemcpyDeviceToHost));
-  if (!quant && sf) HIP_TRY(hipMemcpy(sf, d2.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+  if (quant) to_host(q, d1, (size_t)N * nP);
+  if (!quant && cdf) to_host(cdf, d1, N);
+  if (!quant && sf) to_host(sf, d2, N);
 }
 
 int hmogp_predictive_cdf(int32_t device, int32_t lik_id, double lik_param, int32_t gh_T, int64_t N, const double* y, const double* m,
@@ -762,18 +683,15 @@ int hmogp_predict_quantile(hmogp_handle h, int32_t t, const double* Xnew, int64_
 int hmogp_sample(int32_t device, int32_t lik_id, double lik_param, int64_t N, uint64_t seed, const double* F, double* Y) {
   return guarded(nullptr, [&] {
     check_trials_first(lik_id, lik_param);
-    need_device(device);
-    if (lik_id == HMOGP_LIK_GAUSSIAN && !(lik_param > 0.0)) lik_param = 0.5;
-    const int J = lik_dimf(lik_id, lik_param);
-    check_lik_param(lik_id, lik_param);
+    const int J = block_begin(device, lik_id, lik_param);
     if (J < 1 || J > HMOGP_MAXJ || N <= 0 || !F || !Y) throw EngineError{HMOGP_E_INVALID, "bad arguments"};
     const int Jy = lik_id == HMOGP_LIK_DIRICHLET ? J : 1;   // columns of Y (Weibull: event times only; Binomial, Beta-Binomial: counts only)
     DevBuf dF, dY;
-    dF.ensure(sizeof(double) * N * J), dY.ensure(sizeof(double) * N * Jy);
-    HIP_TRY(hipMemcpy(dF.p, F, sizeof(double) * N * J, hipMemcpyHostToDevice));
+    dY.ensure(sizeof(double) * N * Jy);
+    to_device(dF, F, (size_t)N * J);
     launch_sample(lik_id, J, lik_param, N, seed, dF.d(), dY.d(), nullptr);
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(Y, dY.p, sizeof(double) * N * Jy, hipMemcpyDeviceToHost));
+    to_host(Y, dY, (size_t)N * Jy);
   });
 }
 

@@ -107,7 +107,7 @@ struct GemmArgs {
   // Uses: forward contraction against T = tril(C) + tril(C^T,-1) when only the quadratic forms k^T C k are wanted (b_tri
   // = +1, half the products); S = L L^T, (L L^T)^-1 = Linv^T Linv, dL/dS L and the triangular-inverse merges.
   int a_tri = 0, b_tri = 0;
-  // Exact-zero windows (rowpass.hip: launch_windows): K^ = s2 exp(-r2/2) underflows to exactly 0.0 beyond r ~ 38.6
+  // Exact-zero windows (kuf.hip: launch_windows): K^ = s2 exp(-r2/2) underflows to exactly 0.0 beyond r ~ 38.6
   // lengthscales, so for spatially sorted rows it is banded.  role 1: win[2*ti], win[2*ti+1] = [lo, hi) column range
   // (multiples of 16) outside which every entry of row tile ti is exactly zero -> column tiles outside it are skipped
   // and the K loop runs over the range only.  role 2: win[2*b], win[2*b+1] = [lo, hi) row range outside which column

@@ -11,7 +11,7 @@
 //               parameter-gradient assembly of svmogp.py:101-166.
 // There is no CPU fallback anywhere in this file.
 // [r6] This file keeps the orchestration of one evaluation (set-up, parameter upload, mode decision, begin / finish).  The
-// other host-side pieces live in engine_rows / engine_linalg / engine_comm / engine_graph / engine_optim / abi .hip; shared
+// other host-side pieces live in engine_rows / engine_linalg / engine_comm / engine_graph / engine_optim / lik_host / abi .hip; shared
 // declarations in engine_impl.h.
 #include "engine_impl.h"
 
@@ -170,25 +170,10 @@ void hmogp_engine::init(const hmogp_config* c) {
 void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long long N) {
   if (t < 0 || t >= T || N < 0 || (N > 0 && (!X || !Y))) throw EngineError{HMOGP_E_INVALID, "bad task data"};
   Task& k = tasks[t];
+  // Y is checked, and what the row kernels read of it laid out (the rows' own cut points, log y_k, (log y, delta), (k, n, lc): all of
+  // them depend on the data only), before the task's state changes
   std::vector<double> cuts;
-  if (k.lik == HMOGP_LIK_ORDINAL && N > 0) {  // the rows' own cut points depend on the data only; a label that is not an integer in
-    cuts.resize(2 * (size_t)N);               // 1..K is refused before the task's state changes
-    ordinal_row_cuts(task_table(k), Y, N, cuts.data(), cuts.data() + N);
-  }
-  if (k.lik == HMOGP_LIK_DIRICHLET && N > 0) {   // Y is [N, K]; checked, and its logarithm laid out [K][N], before the state changes
-    cuts.resize((size_t)k.dimf * N);
-    dirichlet_log_rows(k.dimf, Y, N, cuts.data());
-  }
-  if (k.lik == HMOGP_LIK_NEGBINOMIAL && N > 0) negbinomial_check_rows(Y, N);   // counts, checked before the task's state changes
-  if (k.lik == HMOGP_LIK_ZIPOISSON && N > 0) zipoisson_check_rows(Y, N);
-  if (k.lik == HMOGP_LIK_WEIBULL && N > 0) {   // Y is [N, 2] = (y, delta); checked, and (log y, delta) laid out [2][N], before the state changes
-    cuts.resize(2 * (size_t)N);
-    weibull_check_rows(Y, N, cuts.data());
-  }
-  if ((k.lik == HMOGP_LIK_BINOMIAL || k.lik == HMOGP_LIK_BETABINOMIAL) && N > 0) {   // Y is [N, 2] = (k, n); checked, and (k, n, lc) laid out
-    cuts.resize(3 * (size_t)N);                                                      // [3][N], before the state changes
-    binomial_check_rows(k.lik, Y, N, cuts.data());
-  }
+  if (N > 0) cuts = lik_y_image(k.lik, k.lik == HMOGP_LIK_ORDINAL ? &task_table(k) : nullptr, k.dimf, Y, N);
   k.N = N;
   began = false;
   staged_key.clear();
@@ -198,7 +183,7 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
   k.Y.ensure(sizeof(double) * N * k.dimy());
   HIP_TRY(hipMemcpy(k.X.p, X, sizeof(double) * N * P, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(k.Y.p, Y, sizeof(double) * N * k.dimy(), hipMemcpyHostToDevice));
-  if (k.lik == HMOGP_LIK_POISSON || k.lik == HMOGP_LIK_NEGBINOMIAL || k.lik == HMOGP_LIK_ZIPOISSON) {  // gammaln(y+1) depends on the data only (poisson.py:33)
+  if (lik_yaux_gammaln(k.lik)) {  // gammaln(y+1) depends on the data only (poisson.py:33)
     k.Yaux.ensure(sizeof(double) * N);
     launch_gammaln1p(k.Y.d(), k.Yaux.d(), N, st);
     HIP_TRY(hipStreamSynchronize(st));
@@ -212,7 +197,7 @@ void hmogp_engine::set_task_data(int t, const double* X, const double* Y, long l
     k.Ylo.ensure(sizeof(double) * 2 * N);
     HIP_TRY(hipMemcpy(k.Ylo.p, cuts.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
   }
-  if (k.lik == HMOGP_LIK_BINOMIAL || k.lik == HMOGP_LIK_BETABINOMIAL) {   // lc depends on the data only, like gammaln(y+1) above
+  if (lik_has_trials(k.lik)) {   // lc depends on the data only, like gammaln(y+1) above
     k.Ylo.ensure(sizeof(double) * 2 * N), k.Yaux.ensure(sizeof(double) * N);
     HIP_TRY(hipMemcpy(k.Ylo.p, cuts.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(k.Yaux.p, cuts.data() + 2 * N, sizeof(double) * N, hipMemcpyHostToDevice));

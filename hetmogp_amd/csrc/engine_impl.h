@@ -1,8 +1,9 @@
 // engine_impl.h -- internal declarations shared by the host-side translation units of the engine (engine.hip: orchestration of one
 // evaluation; engine_rows.hip: the replicated M x M chain and the row pass; engine_linalg.hip: jitchol ladder and the blocked
 // triangular solves; engine_comm.hip: the RCCL exchange step; engine_graph.hip: hipGraph capture of the small path;
-// engine_optim.hip: device-resident q(u) optimisers, natural gradient, prediction, the raw-gradient debug export; abi.hip: the
-// C ABI of include/hetmogp_hip.h).  [r6] engine.hip was ONE 2 720-line translation unit: split without a
+// engine_optim.hip: device-resident q(u) optimisers, natural gradient, prediction, the raw-gradient debug export; lik_host.hip: what
+// the host knows about the likelihood families; lik_param.hip: the families' own parameters; abi.hip: the C ABI of
+// include/hetmogp_hip.h).  [r6] engine.hip was ONE 2 720-line translation unit: split without a
 // behaviour change -- every function body is the one it was.  Not part of the public interface.
 #pragma once
 #include <algorithm>
@@ -48,6 +49,7 @@ static_assert((int)ncclSuccess == hm_nccl::Success && (int)ncclInProgress == hm_
 #include "common.h"
 #include "post.h"
 #include "rowpass.h"
+#include "lik_launch.h"
 #include "small_model.h"
 
 namespace hmogp_detail {
@@ -107,7 +109,7 @@ struct Task {
   double qparam = 0.0;   // what the quadrature kernels get as lik_param: `param`, but sigma for Ordinal (whose param is a table id)
   // Weibull: Ylo is the [2][N] image (log y, delta) of the task's [N, 2] Y.  Binomial, Beta-Binomial: Ylo is the
   // [2][N] image (k, n) of the task's [N, 2] Y and Yaux holds lc = lgamma(n+1) - lgamma(k+1) - lgamma(n-k+1)
-  bool two_col() const { return lik == HMOGP_LIK_WEIBULL || lik == HMOGP_LIK_BINOMIAL || lik == HMOGP_LIK_BETABINOMIAL; }
+  bool two_col() const { return lik == HMOGP_LIK_WEIBULL || lik_has_trials(lik); }
   const double* quad_y() const { return (lik == HMOGP_LIK_ORDINAL || lik == HMOGP_LIK_DIRICHLET || two_col()) ? Ylo.d() : Y.d(); }   // first per-row value of the quadrature
   long long quad_ldy() const { return (lik == HMOGP_LIK_DIRICHLET || two_col()) ? N : 0; }   // row stride of quad_y() where a row has several values (QuadArgs::ldy)
   int dimy() const { return lik == HMOGP_LIK_DIRICHLET ? dimf : (two_col() ? 2 : 1); }   // columns of the task's Y
@@ -130,14 +132,15 @@ struct LikGradArgs {
   const double *Wd = nullptr, *kapd = nullptr, *vard = nullptr;   // device-resident [Q][Df], [Q][Df], [Q]
   double* partials = nullptr;                                     // [blocks][nout]
 };
-int lik_dparam_cols(int lik);   // columns of hmogp_var_exp_dparam's output (0: the family has no parameters)
 // y: [N], Ordinal [2][N] (lower, upper cut points); m, v: [N][dim_f]; out: [N][lik_dparam_cols]; Ordinal: `param` is the table id
 void launch_var_exp_dparam(int lik, double param, long long N, const double* y, const double* m, const double* v, double* out,
                            hipStream_t s);
 // dst[0 .. nout) += (scaled ? *scaled : scale) * sum over the segment's rows, block partials summed in a fixed order
 void launch_lik_grad(const LikGradArgs& a, double* dst, double scale, const double* scaled, hipStream_t s);
 
+// ---- the families on the host (lik_host.hip) ----
 int lik_dimf(int lik, double param);
+int lik_dparam_cols(int lik);   // columns of hmogp_var_exp_dparam's output (0: the family has no parameters)
 void check_lik_param(int lik, double param);  // HMOGP_E_INVALID for a parameter the likelihood has no value for (Student: nu;
                                               // Ordinal: an id hmogp_ordinal_table never returned; Dirichlet: K not an integer in
                                               // 2 .. HMOGP_DIRICHLET_MAXK)
@@ -154,14 +157,20 @@ void binomial_check_rows(int lik, const double* y, long long N, double* img);
 void ordinal_row_cuts(const OrdinalTable& tb, const double* y, long long N, double* lo, double* hi);
 // registers (or finds) a table; returns the value to pass as lik_param
 double ordinal_register(int K, const double* edges, double sigma);
-// y of a building block (or new rows of a task) -> device, checked, in the image the row kernels read (abi.hip): [N]; Ordinal [2][N] cut points
-// by `tb`, or by the registry entry `lik_param` names when tb is null; Dirichlet [K][N] log y_k; Weibull [2][N] (log y, delta)
+// A family's Y [N] rows, checked (HMOGP_E_INVALID), and the image of it the row kernels read, through the functions above: Ordinal [2][N] cut
+// points by `tb`; Dirichlet [K][N] log y_k; Weibull [2][N] (log y, delta); Binomial, Beta-Binomial [3][N] (k, n, lc).  Empty for every other
+// family: its Y goes to the device as it is.  Shared by hmogp_set_task_data and upload_y_image, each with its own copies to the device.
+std::vector<double> lik_y_image(int lik, const OrdinalTable* tb, int K, const double* y, long long N);
+// y of a building block (or new rows of a task) -> device, checked, in that image, or as it is: Ordinal by `tb`, or by the registry entry
+// `lik_param` names when tb is null
 void upload_y_image(int lik_id, double lik_param, const OrdinalTable* tb, const double* y, long long N, DevBuf& dy);
 // y [N] of the predictive cdf -> device, in the image predq.hip reads: Weibull log y (-inf for y <= 0: the row is (0, 1)); Ordinal
 // the [2][N] cut points of upload_y_image (labels checked); every other family as it is
 void upload_y_cdf(int lik_id, double lik_param, const OrdinalTable* tb, const double* y, long long N, DevBuf& dy);
 // nodes per dimension of the cdf / quantile kernels: 0 = 20; HMOGP_E_INVALID for a family predq.hip refuses (with its reason) or another gh_T
 int predq_nodes(int lik_id, int gh_T);
+// nodes per dimension of the deterministic rule: 0 = the default, 20, but 10 for Categorical and Dirichlet, which take no other
+int lpd_nodes(int lik_id, int gh_T);
 
 // Row ranges per weighted-Gram launch: a multiple of 8 (one range per XCD at a time), each >= 32 k-steps of 16 rows,
 // enough blocks (lower tiles x ranges) for >= 8 rounds over the 256 CUs, at most KS_MAX slabs.

@@ -18,7 +18,8 @@
 #include "gh_tables.h"
 #include "../../include/hetmogp_hip.h"
 
-#include "rowpass.h"  // HMOGP_MAXJ / HMOGP_MAXQ
+#include "rowpass.h"     // HMOGP_MAXJ / HMOGP_MAXQ
+#include "lik_launch.h"  // lik_lanes, lik_pred_lanes and the other compile-time family facts; OrdinalTable
 
 #define LIM_VAL 709.782712893384      // log(DBL_MAX): GPy safe_exp clip
 #define SQRT_DBL_MAX 1.3407807929942596e154  // GPy safe_square clip
@@ -1361,19 +1362,6 @@ __device__ __forceinline__ void lik_dirichlet_sample(RowRng& g, const double* f,
   }
 }
 
-// lanes per row of a likelihood's predictive rule
-__host__ __device__ constexpr int lik_pred_lanes(int lik) {
-  return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_GAMMA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_DIRICHLET) ? 64 : 1;
-}
-
-// lanes per row of a likelihood
-__host__ __device__ constexpr int lik_lanes(int lik) {
-  return (lik == HMOGP_LIK_BETA || lik == HMOGP_LIK_CATEGORICAL || lik == HMOGP_LIK_STUDENT || lik == HMOGP_LIK_DIRICHLET ||
-          lik == HMOGP_LIK_NEGBINOMIAL || lik == HMOGP_LIK_WEIBULL || lik == HMOGP_LIK_BETABINOMIAL || lik == HMOGP_LIK_ZIPOISSON)
-             ? 64
-             : 1;
-}
-
 // Dispatch.  For 64-lane likelihoods every lane of the wave must call with the same row; the result is valid in
 // every lane.  `etab` (per-wave LDS, HMOGP_ETAB doubles) is used by the one-wave-per-row likelihoods.
 // CATD: number of functions (K-1) of a Categorical likelihood -- a template parameter so that each K gets its own register
@@ -1585,7 +1573,6 @@ __device__ __forceinline__ void lik_cdf_sf(double y, double yaux, const double* 
 // on the host), and lc = lgamma(n+1) - lgamma(k+1) - lgamma(n-k+1) is formed once per row on the host, as gammaln(y+1) is for Poisson.
 // The dispatchers above hand the row over as (y, param, yaux) = (k, n, lc): the task's lik_param is the trial count n* of `predictive` and
 // `sample` only (no y reaches them) and is ignored wherever y carries n.  Appended, like the sections above, so that nothing in front changes.
-__host__ __device__ constexpr bool lik_has_trials(int lik) { return lik == HMOGP_LIK_BINOMIAL || lik == HMOGP_LIK_BETABINOMIAL; }
 __device__ __forceinline__ double lik_pred_trials(double param) { return param > 0.0 ? param : 1.0; }   // 0.0 means 1 (checked on the host)
 
 // ---- Binomial, T = 20, one lane per row.  Bernoulli's link and clip, p = clip(e^f / (1 + e^f), 1e-9, 1 - 1e-9), and its expression shapes:

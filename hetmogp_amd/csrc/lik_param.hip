@@ -9,6 +9,7 @@
 // Declarations: engine_impl.h.
 #include "engine_impl.h"
 #include "lik_device.h"
+#include "lik_dispatch.h"
 
 namespace {
 
@@ -132,36 +133,36 @@ __global__ __launch_bounds__(256) void lik_grad_reduce_kernel(const double* __re
 
 namespace hmogp_detail {
 
-int lik_dparam_cols(int lik) {
-  return (lik == HMOGP_LIK_GAUSSIAN || lik == HMOGP_LIK_STUDENT) ? 1 : (lik == HMOGP_LIK_ORDINAL ? 3 : 0);
-}
+// the three families with parameters of their own (lik_dparam_cols != 0), as a compile-time fact for the two launchers below
+constexpr bool has_own_params(int lik) { return lik == HMOGP_LIK_GAUSSIAN || lik == HMOGP_LIK_STUDENT || lik == HMOGP_LIK_ORDINAL; }
 
 void launch_var_exp_dparam(int lik, double param, long long N, const double* y, const double* m, const double* v, double* out,
                            hipStream_t s) {
   if (N <= 0) return;
+  if (!has_own_params(lik)) throw EngineError{HMOGP_E_INVALID, "this likelihood has no parameters of its own"};
   const dim3 grid((unsigned)((N * lik_lanes(lik) + 255) / 256));
-  switch (lik) {
-    case HMOGP_LIK_GAUSSIAN: hipLaunchKernelGGL((var_exp_dparam_kernel<HMOGP_LIK_GAUSSIAN>), grid, dim3(256), 0, s, param, N, y, m, v, out); break;
-    case HMOGP_LIK_STUDENT: hipLaunchKernelGGL((var_exp_dparam_kernel<HMOGP_LIK_STUDENT>), grid, dim3(256), 0, s, param, N, y, m, v, out); break;
-    case HMOGP_LIK_ORDINAL:
-      hipLaunchKernelGGL((var_exp_dparam_kernel<HMOGP_LIK_ORDINAL>), grid, dim3(256), 0, s, ordinal_table(param).sigma, N, y, m, v, out);
-      break;
-    default: throw EngineError{HMOGP_E_INVALID, "this likelihood has no parameters of its own"};
-  }
+  visit_family(lik, 0, [&](auto fam) {
+    constexpr int L = decltype(fam)::LIK;
+    if constexpr (has_own_params(L)) {
+      if constexpr (L == HMOGP_LIK_ORDINAL) param = ordinal_table(param).sigma;
+      hipLaunchKernelGGL((var_exp_dparam_kernel<L>), grid, dim3(256), 0, s, param, N, y, m, v, out);
+    } else {
+      throw EngineError{HMOGP_E_INVALID, "this likelihood has no parameters of its own"};
+    }
+  });
 }
 
 long long lik_grad_blocks(int lik, long long n) { return (n * lik_lanes(lik) + 255) / 256; }
 
 void launch_lik_grad(const LikGradArgs& a, double* dst, double scale, const double* scaled, hipStream_t s) {
-  if (a.N <= 0) return;
+  if (a.N <= 0 || !has_own_params(a.lik)) return;   // (a family without parameters adds nothing)
   const long long nb = lik_grad_blocks(a.lik, a.N);
   const dim3 grid((unsigned)nb);
-  switch (a.lik) {
-    case HMOGP_LIK_GAUSSIAN: hipLaunchKernelGGL((lik_grad_kernel<HMOGP_LIK_GAUSSIAN>), grid, dim3(256), 0, s, a); break;
-    case HMOGP_LIK_STUDENT: hipLaunchKernelGGL((lik_grad_kernel<HMOGP_LIK_STUDENT>), grid, dim3(256), 0, s, a); break;
-    case HMOGP_LIK_ORDINAL: hipLaunchKernelGGL((lik_grad_kernel<HMOGP_LIK_ORDINAL>), grid, dim3(256), 0, s, a); break;
-    default: return;
-  }
+  visit_family(a.lik, 0, [&](auto fam) {
+    constexpr int L = decltype(fam)::LIK;
+    if constexpr (has_own_params(L)) hipLaunchKernelGGL((lik_grad_kernel<L>), grid, dim3(256), 0, s, a);
+    else throw HipError{hipErrorInvalidValue, "lik_grad: this likelihood has no parameters of its own", __FILE__, __LINE__};
+  });
   hipLaunchKernelGGL(lik_grad_reduce_kernel, dim3(a.nout), dim3(256), 0, s, a.partials, nb, a.nout, dst, scale, scaled);
 }
 

@@ -5,8 +5,10 @@
 // lik_dirichlet_logpdf; Gamma and Beta: lik_gamma_logpdf / lik_beta_logpdf).  Gaussian is the closed form log N(y; m, sigma^2 + v)
 // (ess = +inf), HetGaussian integrates f0 analytically: T nodes over f1 of log N(y; m0, v0 + safe_exp(f1)).
 // Two kernels, the split quad_kernel makes: rules of at most 20 nodes run one lane per row, the tensor rules one wave per row (four
-// rows per block), nodes strided over the lanes.  A translation unit of its own: nothing of rowpass.hip changes.
+// rows per block), nodes strided over the lanes.  Declarations: lik_launch.h.
+#include "lik_launch.h"
 #include "lik_device.h"
+#include "lik_dispatch.h"
 
 namespace {
 
@@ -62,7 +64,7 @@ __global__ __launch_bounds__(256) void lpd_lane_kernel(double param, int T, long
       lpd_add(mx, s1, s2, gh_wn(T, i), -0.5 * log(2.0 * M_PI) - 0.5 * log(var) - 0.5 * (d2 / var));
     }
   } else {
-    const double yaux = LIK == HMOGP_LIK_POISSON ? lgamma(yy + 1.0)
+    const double yaux = lik_yaux_gammaln(LIK) ? lgamma(yy + 1.0)
                                                  : (LIK == HMOGP_LIK_ORDINAL ? y[ldy + n] : (lik_has_trials(LIK) ? y[2 * ldy + n] : 0.0));
     if constexpr (lik_has_trials(LIK)) param = y[ldy + n];   // Binomial: y is [3][ldy] = (k, n, lc); the row's own n
     const double s = sqrt(2.0 * v0);
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(256) void lpd_wave_kernel(double param, int T, long
   }
   __builtin_amdgcn_wave_barrier();  // written and read by this wave only
   const double yy = y[n];
-  const double yaux = (LIK == HMOGP_LIK_NEGBINOMIAL || LIK == HMOGP_LIK_ZIPOISSON) ? lgamma(yy + 1.0)
+  const double yaux = lik_yaux_gammaln(LIK) ? lgamma(yy + 1.0)
                                                    : (LIK == HMOGP_LIK_WEIBULL ? y[ldy + n] : (lik_has_trials(LIK) ? y[2 * ldy + n] : 0.0));
   if constexpr (lik_has_trials(LIK)) param = y[ldy + n];   // Beta-Binomial: y is [3][ldy] = (k, n, lc); the row's own n
   double ly[LIK == HMOGP_LIK_DIRICHLET ? JD : 1];
@@ -149,51 +151,19 @@ __global__ __launch_bounds__(256) void lpd_wave_kernel(double param, int T, long
 void launch_log_predictive_gh(const LpdArgs& a, hipStream_t s) {
   if (a.N <= 0) return;
   const dim3 glane((unsigned)((a.N + 255) / 256)), gwave((unsigned)((a.N + 3) / 4));
-#define LANE(L) \
-  hipLaunchKernelGGL((lpd_lane_kernel<L>), glane, dim3(256), 0, s, a.param, a.T, a.N, a.y, a.ldy, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.lpd, a.ess)
-#define WAVE(L, JD) \
-  hipLaunchKernelGGL((lpd_wave_kernel<L, JD>), gwave, dim3(256), 0, s, a.param, a.T, a.N, a.y, a.ldy, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.lpd, a.ess)
-  const bool tensor10 = a.lik == HMOGP_LIK_CATEGORICAL || a.lik == HMOGP_LIK_DIRICHLET;
-  if (tensor10 ? a.T != 10 : (a.T != 10 && a.T != 20))
+  if (lik_tensor10(a.lik) ? a.T != 10 : (a.T != 10 && a.T != 20))
     throw HipError{hipErrorInvalidValue, "log predictive density: nodes per dimension must be 10 or 20 (Categorical, Dirichlet: 10)", __FILE__, __LINE__};
-  switch (a.lik) {
-    case HMOGP_LIK_GAUSSIAN: LANE(HMOGP_LIK_GAUSSIAN); break;
-    case HMOGP_LIK_BERNOULLI: LANE(HMOGP_LIK_BERNOULLI); break;
-    case HMOGP_LIK_POISSON: LANE(HMOGP_LIK_POISSON); break;
-    case HMOGP_LIK_EXPONENTIAL: LANE(HMOGP_LIK_EXPONENTIAL); break;
-    case HMOGP_LIK_ORDINAL: LANE(HMOGP_LIK_ORDINAL); break;
-    case HMOGP_LIK_BINOMIAL: LANE(HMOGP_LIK_BINOMIAL); break;
-    case HMOGP_LIK_HETGAUSSIAN: LANE(HMOGP_LIK_HETGAUSSIAN); break;
-    case HMOGP_LIK_GAMMA: WAVE(HMOGP_LIK_GAMMA, 2); break;
-    case HMOGP_LIK_BETA: WAVE(HMOGP_LIK_BETA, 2); break;
-    case HMOGP_LIK_STUDENT: WAVE(HMOGP_LIK_STUDENT, 2); break;
-    case HMOGP_LIK_NEGBINOMIAL: WAVE(HMOGP_LIK_NEGBINOMIAL, 2); break;
-    case HMOGP_LIK_WEIBULL: WAVE(HMOGP_LIK_WEIBULL, 2); break;
-    case HMOGP_LIK_BETABINOMIAL: WAVE(HMOGP_LIK_BETABINOMIAL, 2); break;
-    case HMOGP_LIK_ZIPOISSON: WAVE(HMOGP_LIK_ZIPOISSON, 2); break;
-    case HMOGP_LIK_CATEGORICAL:
-      switch (a.J) {
-        case 1: WAVE(HMOGP_LIK_CATEGORICAL, 1); break;
-        case 2: WAVE(HMOGP_LIK_CATEGORICAL, 2); break;
-        case 3: WAVE(HMOGP_LIK_CATEGORICAL, 3); break;
-        case 4: WAVE(HMOGP_LIK_CATEGORICAL, 4); break;
-        case 5: WAVE(HMOGP_LIK_CATEGORICAL, 5); break;
-        case 6: WAVE(HMOGP_LIK_CATEGORICAL, 6); break;
-        case 7: WAVE(HMOGP_LIK_CATEGORICAL, 7); break;
-        case 8: WAVE(HMOGP_LIK_CATEGORICAL, 8); break;
-        default: throw HipError{hipErrorInvalidValue, "Categorical needs 2 <= K <= 9", __FILE__, __LINE__};
-      }
-      break;
-    case HMOGP_LIK_DIRICHLET:
-      switch (a.J) {
-        case 2: WAVE(HMOGP_LIK_DIRICHLET, 2); break;
-        case 3: WAVE(HMOGP_LIK_DIRICHLET, 3); break;
-        case 4: WAVE(HMOGP_LIK_DIRICHLET, 4); break;
-        default: throw HipError{hipErrorInvalidValue, "Dirichlet needs 2 <= K <= HMOGP_DIRICHLET_MAXK", __FILE__, __LINE__};
-      }
-      break;
-    default: throw HipError{hipErrorInvalidValue, "unknown likelihood id", __FILE__, __LINE__};
-  }
-#undef LANE
-#undef WAVE
+  visit_family(a.lik, a.J, [&](auto fam) {
+    constexpr int L = decltype(fam)::LIK, D = decltype(fam)::D;
+    // rules of at most 20 nodes: one lane per row; the tensor rules of the two-function families and of Categorical / Dirichlet: one wave
+    constexpr bool lane = L == HMOGP_LIK_GAUSSIAN || L == HMOGP_LIK_BERNOULLI || L == HMOGP_LIK_POISSON || L == HMOGP_LIK_EXPONENTIAL ||
+                          L == HMOGP_LIK_ORDINAL || L == HMOGP_LIK_BINOMIAL || L == HMOGP_LIK_HETGAUSSIAN;
+    constexpr bool wave2 = L == HMOGP_LIK_GAMMA || L == HMOGP_LIK_BETA || L == HMOGP_LIK_STUDENT || L == HMOGP_LIK_NEGBINOMIAL ||
+                           L == HMOGP_LIK_WEIBULL || L == HMOGP_LIK_BETABINOMIAL || L == HMOGP_LIK_ZIPOISSON;
+    static_assert(lane || wave2 || lik_tensor10(L), "launch_log_predictive_gh: a family with neither a lane nor a wave rule");
+    if constexpr (lane)
+      hipLaunchKernelGGL((lpd_lane_kernel<L>), glane, dim3(256), 0, s, a.param, a.T, a.N, a.y, a.ldy, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.lpd, a.ess);
+    else
+      hipLaunchKernelGGL((lpd_wave_kernel<L, wave2 ? 2 : D>), gwave, dim3(256), 0, s, a.param, a.T, a.N, a.y, a.ldy, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.lpd, a.ess);
+  });
 }

@@ -15,7 +15,9 @@
 // the same nodes), at most PQ_MAXNEWTON of them; a candidate outside the bracket, or none left, is replaced by the midpoint of the
 // bracket's ORDERED BIT PATTERNS, which closes any bracket of doubles in at most 64 halvings.  The iterate of the wave kernel is formed
 // from wave_sum's results, which are the same bits in all 64 lanes, so its branches do not diverge.
+#include "lik_launch.h"
 #include "lik_device.h"
+#include "lik_dispatch.h"
 
 #define PQ_MAXEVAL 128
 #define PQ_MAXDBL 64
@@ -354,6 +356,12 @@ __global__ __launch_bounds__(256) void pquant_wave_kernel(long long N, int nP, P
   }
 }
 
+// the five of the six families whose rule runs one lane per row (Weibull, the sixth: one wave per row)
+constexpr bool predq_lane(int lik) {
+  return lik == HMOGP_LIK_GAUSSIAN || lik == HMOGP_LIK_HETGAUSSIAN || lik == HMOGP_LIK_BERNOULLI || lik == HMOGP_LIK_EXPONENTIAL ||
+         lik == HMOGP_LIK_ORDINAL;
+}
+
 }  // namespace
 
 const char* predq_refusal(int lik) {
@@ -390,19 +398,17 @@ void launch_predictive_cdf(const PqArgs& a, hipStream_t s) {
   predq_check(a);
   if (a.N <= 0) return;
   const dim3 glane((unsigned)((a.N + 255) / 256)), gwave((unsigned)((a.N + 3) / 4));
-#define LANE(L) \
-  hipLaunchKernelGGL((pcdf_lane_kernel<L>), glane, dim3(256), 0, s, a.param, a.T, a.N, a.y, a.ldy, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.cdf, a.sf)
-  switch (a.lik) {
-    case HMOGP_LIK_GAUSSIAN: LANE(HMOGP_LIK_GAUSSIAN); break;
-    case HMOGP_LIK_HETGAUSSIAN: LANE(HMOGP_LIK_HETGAUSSIAN); break;
-    case HMOGP_LIK_BERNOULLI: LANE(HMOGP_LIK_BERNOULLI); break;
-    case HMOGP_LIK_EXPONENTIAL: LANE(HMOGP_LIK_EXPONENTIAL); break;
-    case HMOGP_LIK_ORDINAL: LANE(HMOGP_LIK_ORDINAL); break;
-    default:
+  visit_family(a.lik, 0, [&](auto fam) {   // (predq_check let only the six families through: none of them has a function count)
+    constexpr int L = decltype(fam)::LIK;
+    if constexpr (predq_lane(L)) {
+      hipLaunchKernelGGL((pcdf_lane_kernel<L>), glane, dim3(256), 0, s, a.param, a.T, a.N, a.y, a.ldy, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.cdf, a.sf);
+    } else if constexpr (L == HMOGP_LIK_WEIBULL) {
       if (a.T == 10) hipLaunchKernelGGL((pcdf_wave_kernel<10>), gwave, dim3(256), 0, s, a.N, a.y, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.cdf, a.sf);
       else hipLaunchKernelGGL((pcdf_wave_kernel<20>), gwave, dim3(256), 0, s, a.N, a.y, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.cdf, a.sf);
-  }
-#undef LANE
+    } else {
+      throw HipError{hipErrorInvalidValue, predq_refusal(L), __FILE__, __LINE__};
+    }
+  });
 }
 
 void launch_predictive_quantile(const PqArgs& a, hipStream_t s) {
@@ -414,21 +420,18 @@ void launch_predictive_quantile(const PqArgs& a, hipStream_t s) {
   PqProbs pr;
   for (int i = 0; i < HMOGP_QUANT_MAXP; ++i) pr.p[i] = i < a.nP ? a.p[i] : 0.5;
   const OrdinalTable tb = a.table ? *a.table : OrdinalTable();
-#define LANE(L, TT) \
-  hipLaunchKernelGGL((pquant_lane_kernel<L, TT>), glane, dim3(256), 0, s, a.param, tb, a.N, a.nP, pr, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.q)
-#define LANE2(L)          \
-  if (a.T == 10) LANE(L, 10); \
-  else LANE(L, 20)
-  switch (a.lik) {
-    case HMOGP_LIK_GAUSSIAN: LANE(HMOGP_LIK_GAUSSIAN, 10); break;   // (closed form: no nodes)
-    case HMOGP_LIK_ORDINAL: LANE(HMOGP_LIK_ORDINAL, 10); break;     // (closed form: no nodes)
-    case HMOGP_LIK_HETGAUSSIAN: LANE2(HMOGP_LIK_HETGAUSSIAN); break;
-    case HMOGP_LIK_BERNOULLI: LANE2(HMOGP_LIK_BERNOULLI); break;
-    case HMOGP_LIK_EXPONENTIAL: LANE2(HMOGP_LIK_EXPONENTIAL); break;
-    default:
+  visit_family(a.lik, 0, [&](auto fam) {
+    constexpr int L = decltype(fam)::LIK;
+    if constexpr (L == HMOGP_LIK_GAUSSIAN || L == HMOGP_LIK_ORDINAL) {   // (closed form: no nodes)
+      hipLaunchKernelGGL((pquant_lane_kernel<L, 10>), glane, dim3(256), 0, s, a.param, tb, a.N, a.nP, pr, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.q);
+    } else if constexpr (predq_lane(L)) {
+      if (a.T == 10) hipLaunchKernelGGL((pquant_lane_kernel<L, 10>), glane, dim3(256), 0, s, a.param, tb, a.N, a.nP, pr, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.q);
+      else hipLaunchKernelGGL((pquant_lane_kernel<L, 20>), glane, dim3(256), 0, s, a.param, tb, a.N, a.nP, pr, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.q);
+    } else if constexpr (L == HMOGP_LIK_WEIBULL) {
       if (a.T == 10) hipLaunchKernelGGL((pquant_wave_kernel<10>), gwave, dim3(256), 0, s, a.N, a.nP, pr, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.q);
       else hipLaunchKernelGGL((pquant_wave_kernel<20>), gwave, dim3(256), 0, s, a.N, a.nP, pr, a.m, a.v, a.ldf, a.absv ? 1 : 0, a.q);
-  }
-#undef LANE2
-#undef LANE
+    } else {
+      throw HipError{hipErrorInvalidValue, predq_refusal(L), __FILE__, __LINE__};
+    }
+  });
 }

@@ -1,4 +1,6 @@
-// rowpass.h -- launchers of the row-streaming kernels (rowpass.hip).
+// rowpass.h -- launchers of the row-streaming kernels: K_uf and its windows (kuf.hip), the quadrature (quad.hip), the column statistics,
+// reductions and wire format (rowpass.hip), the strict mode's row kernels (strict_rows.hip, trsm_panel.hip), the joint posterior (joint.hip).
+// The per-family building blocks: lik_launch.h.
 #pragma once
 #include "common.h"
 #include "../../include/hetmogp_hip.h"
@@ -52,7 +54,7 @@ struct QuadArgs {
   long long ldy = 0;
 };
 
-// strict q(f): the row statistics of the solve-based forms (rowpass.hip: strict_rowstats_kernel)
+// strict q(f): the row statistics of the solve-based forms (strict_rows.hip: strict_rowstats_kernel)
 struct StrictRows {
   int phase = 0, M = 0, Q = 1, P = 1, ldz = 0;
   long long n = 0, ldn = 0, sK = 0, sZ = 0;
@@ -145,16 +147,6 @@ struct SmallQuadRed {
   } s[8];
 };
 
-// One registered Ordinal likelihood (hmogp_ordinal_table): K classes, K - 1 cut points, noise scale.  Small enough to
-// travel to the predictive / sampling kernels by value.
-struct OrdinalTable {
-  int K = 0;
-  double sigma = 0.0;
-  double edge[HMOGP_ORDINAL_MAXK - 1];
-};
-// the table behind an Ordinal task's lik_param (engine_linalg.hip; throws HMOGP_E_INVALID for an id that was never handed out)
-const OrdinalTable& ordinal_table(double lik_param);
-
 long long quad_blocks(int lik, long long N);
 // [r5] is there an instantiation of quad_multi_kernel for exactly this set of likelihoods (other than the all-inclusive one, which
 // runs one wave per SIMD)?
@@ -164,58 +156,6 @@ bool quad_multi_specialised(const QuadMulti& m);
 void launch_reduce_rows_multi(const SmallQuadRed& qr, double* dst, hipStream_t s);
 void launch_quad(const QuadArgs& a, hipStream_t s);
 void launch_quad_multi(const QuadMulti& m, hipStream_t s);   // fills blk0 / part0 of the segments; partials laid out segment by segment
-// Ordinal: `param` is the table id in all four building blocks below, and `y` of launch_var_exp / launch_log_predictive is [2][N]:
-// the rows' lower cut points, then their upper ones (ordinal_row_cuts).  Dirichlet: `param` is K, `y` is [K][N]: log y_k (dirichlet_log_rows),
-// launch_predictive writes [N][K] moments and launch_sample [N][K] compositions
-void launch_var_exp(int lik, int J, double param, long long N, const double* y, const double* m, const double* v, double* ve,
-                    double* dm, double* dv, hipStream_t s, unsigned quirks = 0x1fu);
-// K[n][m] = var * exp(-r2/2); X rows have stride ldx, Z rows stride ldz (block q of the M x Q*P inducing array)
-// predictive mean / variance of y: m, v [N][J] -> mean, var [N][Jp]; T = Gauss-Hermite order (10 or 20)
-void launch_predictive(int lik, int J, int Jp, double param, int T, long long N, const double* m, const double* v,
-                       double* mean, double* var, hipStream_t s);
-// out[n] = -log S + logsumexp_s log p(y_n | f_s), f_s ~ N(m_n, diag v_n): Monte-Carlo log predictive density per row
-void launch_log_predictive(int lik, int J, double param, long long N, int S, unsigned long long seed, const double* y,
-                           const double* m, const double* v, double* out, hipStream_t s);
-// Deterministic log predictive density per row (logpred.hip): lpd[n] = log of the Gauss-Hermite tensor rule of p(y_n | f)
-// under q(f) = N(m_n, diag v_n), ess[n] = the rule's effective number of nodes (nullptr: not wanted).  `y` is the image the other
-// building blocks read ([N]; Ordinal [2][ldy] cut points; Weibull [2][ldy]; Dirichlet [K][ldy]); m, v: row n starts at m[n * ldf], so
-// that a task's columns of the engine's [N][Df] q(f) arrays are read in place.  `param`: sigma (Gaussian, Ordinal -- not the table
-// id), nu (Student), K (Categorical, Dirichlet).  T: 10 or 20 nodes per dimension (Categorical, Dirichlet: 10).
-struct LpdArgs {
-  int lik = 0, J = 1, T = 20;
-  double param = 0.0;
-  long long N = 0;
-  const double* y = nullptr;
-  long long ldy = 0;
-  const double *m = nullptr, *v = nullptr;
-  int ldf = 1;
-  bool absv = false;               // take |v| (the engine's q(f) variance, as the facade does)
-  double *lpd = nullptr, *ess = nullptr;
-};
-void launch_log_predictive_gh(const LpdArgs& a, hipStream_t s);
-// Predictive cdf / survival function / quantiles per row (predq.hip) over the same nodes and weights, for Gaussian,
-// HetGaussian, Bernoulli, Exponential, Ordinal and Weibull; m, v, ldf, absv as in LpdArgs.  `y` (cdf only): [N]; Ordinal [2][ldy] cut
-// points (the upper one is read); Weibull [N] log of the time, -inf for a time <= 0.  `param`: sigma (Gaussian, Ordinal -- not the
-// table id).  `table`: the Ordinal table (quantiles only).  cdf / sf: [N], either may be null.  q: [N][nP], p: nP <= HMOGP_QUANT_MAXP
-// probabilities (one outside (0, 1): NaN in its column).  T: 10 or 20.
-struct PqArgs {
-  int lik = 0, T = 20;
-  double param = 0.0;
-  const OrdinalTable* table = nullptr;
-  long long N = 0;
-  const double* y = nullptr;
-  long long ldy = 0;
-  const double *m = nullptr, *v = nullptr;
-  int ldf = 1;
-  bool absv = false;
-  double *cdf = nullptr, *sf = nullptr;
-  int nP = 0;
-  double p[HMOGP_QUANT_MAXP] = {};
-  double* q = nullptr;
-};
-const char* predq_refusal(int lik);   // nullptr for the six families, else the reason the family is refused
-void launch_predictive_cdf(const PqArgs& a, hipStream_t s);
-void launch_predictive_quantile(const PqArgs& a, hipStream_t s);
 // Joint posterior covariance at new inputs (joint.hip): cov[(j, i), (j', i')] = sum_q (w_jq w_j'q + kap_jq [j == j']) k_q(x_i, x_i')
 // + w_jq w_j'q G_q[max(i, i'), min(i, i')] for every pair of the nD functions d[j], one 64 x 64 tile of (i, i') per block; lower tiles
 // computed, their mirror images written from the same registers.  G: [Q][N][N] (only its lower triangle is read); W, kap: [Q][Df];
@@ -233,16 +173,14 @@ void launch_joint_normal(unsigned long long seed, int S, long long n, double* Z,
 // mean[j * N + i] = m[i * Df + d[j]]: the joint vector's function-major mean out of q(f)'s [N][Df] rows (i0: first row of the chunk)
 void launch_joint_gather(const double* m, int Df, const int* d, int nD, long long N, long long i0, long long nrows, double* mean,
                          hipStream_t s);
-// Y[n] ~ p(y | F[n]): the reference's `<likelihood>.samples`, one draw per row, counter-based generator
-void launch_sample(int lik, int J, double param, long long N, unsigned long long seed, const double* F, double* Y,
-                   hipStream_t s);
+// K[n][m] = var * exp(-r2/2); X rows have stride ldx, Z rows stride ldz (block q of the M x Q*P inducing array)
 void launch_rbf(const double* X, int ldx, long long N, int P, const double* Z, int ldz, int M, double var, double ell,
                 double* K, bool same, hipStream_t s, const int* rowwin = nullptr, bool exact = true,
                 const RbfBatch* batch = nullptr);
 void launch_reduce_slabs_lower(const double* slabs, int nslabs, int M, double* dst, bool accumulate, hipStream_t s, int nb = 1,
                                long long sSlabs = 0, long long sDst = 0);
 // exact-zero windows of K^ = k(X, Z) for one (row chunk, latent): rowwin [tiles][2] column range per 128-row tile,
-// colwin [ncb][2] row range per 128-column block, hit [tiles][ncb] scratch (see rowpass.hip)
+// colwin [ncb][2] row range per 128-column block, hit [tiles][ncb] scratch (see kuf.hip)
 void launch_windows(const double* X, long long N, int P, const double* Z, int ldz, int M, double ell, int* rowwin, int* colwin,
                     unsigned char* hit, hipStream_t s);
 void launch_colstats(const double* Kh, const double* Pt, const double* a, const double* alpha, const double* alpha0,
@@ -261,4 +199,3 @@ void launch_wire_copy(double* bundle, double* wire, long long NG, int Q, int M, 
 // inner-protocol debug export: out[m][n] = a[m] gm[n][j] + 2 w gv[n][j] Pt[n][m]   (svmogp_inf.py:157-161), out is [M][N]
 void launch_raw_kmn(const double* a, const double* gm, const double* gv, int J, int j, double w, const double* Pt, int M,
                     long long N, double* out, hipStream_t s);
-void launch_gammaln1p(const double* y, double* out, long long N, hipStream_t s);

@@ -1,6 +1,6 @@
 """Parameter holders with the names the reference's model wiring uses: `RBF` (GPy.kern.RBF as built by
 util.latent_functions_prior, util.py:75-90) and `Coregionalize` (GPy.kern.Coregionalize with rank 1, util.py:120).
-They hold values and gradients only; K_uu / K_uf are built on the GPU (csrc/rowpass.hip)."""
+They hold values and gradients only; K_uu / K_uf are built on the GPU (csrc/kuf.hip)."""
 import numpy as np
 
 from .param import Param

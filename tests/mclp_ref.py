@@ -1,5 +1,5 @@
 """float64 NumPy / SciPy restatement of the Monte-Carlo log predictive density (`hmogp_log_predictive`: `log_predictive_kernel<LIK>` and
-`dirichlet_log_predictive_kernel<K>` of csrc/rowpass.hip), the loader / criterion of its grid tests/golden/mclpgrid.npz
+`dirichlet_log_predictive_kernel<K>` of csrc/lik_blocks.hip), the loader / criterion of its grid tests/golden/mclpgrid.npz
 (tools/make_mclp_grid.py; 50-digit values from tests/mclp_ref_mp.py), the statistics that hold its generator to the normal law, and a
 NumPy emulation of the kernel's own (max, sum-exp) update.
 

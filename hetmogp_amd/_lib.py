@@ -156,6 +156,9 @@ EXPORTS = {
     "hmogp_select_inducing": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32,
                                         C.c_double, C.c_int32, c_int64_p, c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                         c_double_p, c_int32_p]),
+    "hmogp_qf_input_grad": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p,
+                                      C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p]),
+    "hmogp_predict_f_grad": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hmogp_sample": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint64, c_double_p, c_double_p]),
     "hmogp_bench_contraction": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, c_double_p]),
     "hmogp_host_alloc": (C.c_void_p, [C.c_uint64]),

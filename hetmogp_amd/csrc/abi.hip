@@ -337,6 +337,11 @@ int hmogp_sample_f_joint(hmogp_handle h, const double* Xnew, int64_t Nnew, int32
   });
 }
 
+int hmogp_predict_f_grad(hmogp_handle h, const double* Xnew, int64_t Nnew, double* m, double* v, double* dm, double* dv) {
+  if (!h) return guarded(nullptr, [] { throw EngineError{HMOGP_E_INVALID, "hmogp_predict_f_grad: the handle is NULL"}; });
+  return guarded(h, [&] { h->predict_f_grad(Xnew, Nnew, m, v, dm, dv); });
+}
+
 int hmogp_last_timings(hmogp_handle h, double* out_ms, int64_t* launches) {
   if (!h || !out_ms) return HMOGP_E_INVALID;
   for (int c = 0; c < NCAT; ++c) {
@@ -374,6 +379,71 @@ int hmogp_select_inducing(int32_t device, int64_t N, int32_t P, const double* X,
     select_inducing_check(N, P, X, Q, variance, lengthscale, Mmax, tol, n_forced, forced, pivots, Z, dpiv, trace, Mout);   // on the host, first
     need_device(device);
     select_inducing_run(N, P, X, Q, variance, lengthscale, Mmax, tol, n_forced, forced, pivots, Z, dpiv, trace, L, d, Mout);
+  });
+}
+
+// the building block of the input gradients -- any a, any C: A_q = launch_rbf in the named rounding variant, T_q = A_q C_q by
+// the FP64-MFMA GEMM accumulating into a zeroed target, qf_xgrad_kernel, the combine.  Rows go through in chunks (a row's bits do not
+// depend on them).  Every refusal sits in front of need_device.
+int hmogp_qf_input_grad(int32_t device, int64_t N, int32_t P, const double* X, int32_t M, int32_t Q, const double* Z, const double* variance,
+                        const double* lengthscale, int32_t exact, const double* a, const double* C, int32_t Df, const double* W, double* dm,
+                        double* dv) {
+  return guarded(nullptr, [&] {
+    auto refuse = [](const char* what) { throw EngineError{HMOGP_E_INVALID, std::string("hmogp_qf_input_grad: ") + what}; };
+    if (N < 0) refuse("N must be >= 0");
+    if (P < 1 || P > 4) refuse("P must be in 1..4");
+    if (M < 1) refuse("M must be >= 1");
+    if (Q < 1 || Q > HMOGP_MAXQ) refuse("Q must be in 1..HMOGP_MAXQ");
+    if (Df < 1) refuse("Df must be >= 1");
+    if (N > 0) {
+      if (!X) refuse("X is NULL");
+      if (!Z) refuse("Z is NULL");
+      if (!variance) refuse("variance is NULL");
+      if (!lengthscale) refuse("lengthscale is NULL");
+      if (!a) refuse("a is NULL");
+      if (!C) refuse("C is NULL");
+      if (!W) refuse("W is NULL");
+      if (!dm) refuse("dm is NULL");
+      if (!dv) refuse("dv is NULL");
+    }
+    for (int q = 0; q < Q && variance && lengthscale; ++q) {
+      if (!(std::isfinite(variance[q]) && variance[q] > 0.0)) refuse("variance must be finite and > 0");
+      if (!(std::isfinite(lengthscale[q]) && lengthscale[q] > 0.0)) refuse("lengthscale must be finite and > 0");
+    }
+    if (N == 0) return;
+    need_device(device);
+    const long long MM = (long long)M * M;
+    const long long rows = std::min<long long>(N, std::max<long long>(1024, (1LL << 27) / ((long long)M * Q)));
+    DevBuf dX, dZ, dvar, dell, da, dC, dW, dA, dT, dgp, dgc, ddm, ddv;
+    to_device(dX, X, (size_t)N * P), to_device(dZ, Z, (size_t)M * Q * P), to_device(dvar, variance, Q), to_device(dell, lengthscale, Q);
+    to_device(da, a, (size_t)Q * M), to_device(dC, C, (size_t)Q * MM), to_device(dW, W, (size_t)Q * Df);
+    dA.ensure(sizeof(double) * Q * rows * M), dT.ensure(sizeof(double) * Q * rows * M);
+    dgp.ensure(sizeof(double) * Q * rows * P), dgc.ensure(sizeof(double) * Q * rows * P);
+    ddm.ensure(sizeof(double) * N * Df * P), ddv.ensure(sizeof(double) * N * Df * P);
+    for (long long r0 = 0; r0 < N; r0 += rows) {
+      const long long n = std::min(rows, N - r0), sK = n * M;
+      RbfBatch rbt;
+      rbt.nq = Q, rbt.var = dvar.d(), rbt.ell = dell.d(), rbt.sZ = P, rbt.sK = sK;
+      launch_rbf(dX.d() + r0 * P, P, n, P, dZ.d(), Q * P, M, 0.0, 1.0, dA.d(), false, nullptr, nullptr, exact != 0, &rbt);
+      HIP_TRY(hipMemsetAsync(dT.p, 0, sizeof(double) * Q * sK, nullptr));
+      GemmArgs g;
+      g.A = dA.d(), g.lda = M, g.a_kmajor = 0, g.sA = sK;
+      g.B = dC.d(), g.ldb = M, g.b_kmajor = 1, g.sB = MM;
+      g.C = dT.d(), g.ldc = M, g.sC = sK;
+      g.M = (int)n, g.N = M, g.K = M;
+      g.nbatch = Q;
+      g.alpha = 1.0, g.beta = 1.0;
+      launch_gemm_f64(g, nullptr);                                             // T = A C_q
+      XgradArgs xa;
+      xa.P = P, xa.Q = Q, xa.M = M, xa.ldz = Q * P, xa.n = n, xa.sK = sK, xa.ldo = n;
+      xa.A = dA.d(), xa.T = dT.d(), xa.Z = dZ.d(), xa.a = da.d(), xa.ell = dell.d(), xa.X = dX.d() + r0 * P;
+      xa.gp = dgp.d(), xa.gc = dgc.d();
+      launch_qf_xgrad(xa, nullptr);
+      launch_qf_xgrad_combine(dgp.d(), dgc.d(), n, n, Q, Df, P, dW.d(), ddm.d() + r0 * Df * P, ddv.d() + r0 * Df * P, nullptr);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    to_host(dm, ddm, (size_t)N * Df * P), to_host(dv, ddv, (size_t)N * Df * P);
   });
 }
 

@@ -566,6 +566,9 @@ struct hmogp_engine {
   // ladder and S draws F = mean + L z.  mean, cov, L, jitter_out, rung_out may be null where the caller does not want them.
   void joint(const double* Xnew, long long Nnew, int nD, const int* d, double* mean, double* cov, int S, unsigned long long seed,
              double* F, double* Lout, double* jitter_out, int* rung_out);
+  // d m_d / d x_j and d v_d / d x_j (v the signed value predict_f returns) at Xnew, dm / dv [Nnew][Df][P]; m, v (either may
+  // be null) are qf_chunk's own: the bits of predict_f
+  void predict_f_grad(const double* Xnew, long long Nnew, double* m, double* v, double* dm, double* dv);
 
   // ---- likelihood parameters (lik_param.hip) ----
   bool lik_grad_on = false;      // hmogp_lik_grad_enable: persistent

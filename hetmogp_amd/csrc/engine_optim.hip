@@ -442,3 +442,78 @@ void hmogp_engine::joint(const double* Xnew, long long Nnew, int nD, const int* 
   if (Lout) HIP_TRY(hipMemcpyAsync(Lout, jL.p, sizeof(double) * n * n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
 }
+
+// gradients of q(f) with respect to the new inputs, dm / dv [Nnew][Df][P] (v the SIGNED value predict_f returns).  The same
+// chunks as predict_f; m and v are qf_chunk's own (the bits of hmogp_predict_f).  A_q is the image the mean was formed with, read back from
+// memory by qf_xgrad_kernel: in the default mode qf_chunk's own K_uf, still in Kh (the forward contraction only reads it); in the strict
+// mode, whose solves overwrite theirs, the same launch_rbf once more, as joint does.  T_q = A_q C_q follows the mode of the evaluation it is taken from, as joint does:
+//   default  T = A C_q                                                                 (the explicit C_q)
+//   strict   R = A Kuu^-1 (row solves against Luu), T1 = R L_q, U = T1 L_q^T - A, T = U Kuu^-1   (C_q is never read)
+// Every product is the existing GEMM ACCUMULATING into a zeroed target (beta = 1): the general FP64-MFMA kernel whatever the row count,
+// so a row's bits do not depend on the chunk.  The mean's coefficients are the engine's `a` in both modes.  Every refusal comes before
+// the first device call.
+void hmogp_engine::predict_f_grad(const double* Xnew, long long Nnew, double* m, double* v, double* dm_out, double* dv_out) {
+  if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to predict from"};
+  if (Nnew < 0) throw EngineError{HMOGP_E_INVALID, "predict_f_grad: Nnew must be >= 0"};
+  if (Nnew > 0 && !Xnew) throw EngineError{HMOGP_E_INVALID, "predict_f_grad: Xnew is NULL"};
+  if (Nnew > 0 && (!dm_out || !dv_out)) throw EngineError{HMOGP_E_INVALID, "predict_f_grad: dm and dv must be given"};
+  if (Nnew == 0) return;
+
+  HIP_TRY(hipSetDevice(device));
+  ensure_workspace(std::min(chunk, std::max<long long>(Nnew, 1)));
+  ensure_strict_workspace();           // (the gradients follow the mode of the evaluation they are taken from)
+  const long long ldn = ws_rows, MM = (long long)M * M;
+  DevBuf dX, dm, dv, gA, gT, gR, gU, ggp, ggc, gdm, gdv;
+  dX.ensure(sizeof(double) * ldn * P), dm.ensure(sizeof(double) * ldn * Df), dv.ensure(sizeof(double) * ldn * Df);
+  const long long nmax = std::min(ldn, Nnew);
+  gT.ensure(sizeof(double) * Q * (strict ? nmax : ldn) * M);
+  if (strict) gA.ensure(sizeof(double) * Q * nmax * M), gR.ensure(sizeof(double) * Q * nmax * M), gU.ensure(sizeof(double) * Q * nmax * M);
+  ggp.ensure(sizeof(double) * Q * nmax * P), ggc.ensure(sizeof(double) * Q * nmax * P);
+  gdm.ensure(sizeof(double) * nmax * Df * P), gdv.ensure(sizeof(double) * nmax * Df * P);
+  for (long long r0 = 0; r0 < Nnew; r0 += ldn) {
+    const long long n = std::min(ldn, Nnew - r0), sK = (strict ? n : ldn) * M;   // (default mode: Kh's own stride, for A and T alike)
+    qf_chunk(Xnew + r0 * P, n, dX, dm, dv);
+    const double* A_q = Kh.d();                        // default mode: [Q][ldn * M], the rows qf_chunk's mean was formed with
+    if (strict) {
+      RbfBatch rbt;
+      rbt.nq = Q, rbt.var = dvar.d(), rbt.ell = dell.d(), rbt.sZ = P, rbt.sK = sK;
+      launch_rbf(dX.d(), P, n, P, dZ.d(), Q * P, M, 0.0, 1.0, gA.d(), false, st, nullptr, true, &rbt);   // K_uf as qf_chunk rounds it
+      A_q = gA.d();
+    }
+    // C_[q] += A_[q] op(B_[q]), A_ the n x M rows (row-major, lda = M); batched over the latents
+    auto acc = [&](const double* A_, const double* B_, int b_kmajor, int b_tri, double* C_) {
+      GemmArgs g;
+      g.A = A_, g.lda = M, g.a_kmajor = 0, g.sA = sK;
+      g.B = B_, g.ldb = M, g.b_kmajor = b_kmajor, g.sB = MM, g.b_tri = b_tri;
+      g.C = C_, g.ldc = M, g.sC = sK;
+      g.M = (int)n, g.N = M, g.K = M;
+      g.nbatch = Q;
+      g.alpha = 1.0, g.beta = 1.0;
+      launch_gemm_f64(g, st);
+    };
+    if (strict) {
+      potrs_rows_inplace(gR.d(), sK, Luu.d(), MM, M, n, Q, st, Lsy.d(), gA.d(), rdiag.d(), nullptr, 3, lsym_valid);   // R = A Kuu^-1
+      HIP_TRY(hipMemsetAsync(gU.p, 0, sizeof(double) * Q * sK, st));
+      acc(gR.d(), L.d(), 1, +1, gU.d());                                       // T1 = R L_q   (L_q lower)
+      HIP_TRY(hipMemsetAsync(gR.p, 0, sizeof(double) * Q * sK, st));
+      acc(gU.d(), L.d(), 0, -1, gR.d());                                       // T1 L_q^T     (op(B)[k][j] = L_q[j][k]: zero for k > j)
+      launch_sub(gR.d(), gA.d(), gU.d(), Q * sK, st);                          // U = T1 L_q^T - A
+      potrs_rows_inplace(gT.d(), sK, Luu.d(), MM, M, n, Q, st, Lsy.d(), gU.d(), rdiag.d(), nullptr, 3, lsym_valid);   // T = U Kuu^-1
+    } else {
+      HIP_TRY(hipMemsetAsync(gT.p, 0, sizeof(double) * Q * sK, st));
+      acc(A_q, C.d(), 1, 0, gT.d());                                           // T = A C_q
+    }
+    XgradArgs xa;
+    xa.P = P, xa.Q = Q, xa.M = M, xa.ldz = Q * P, xa.n = n, xa.sK = sK, xa.ldo = n;
+    xa.A = A_q, xa.T = gT.d(), xa.Z = dZ.d(), xa.a = a.d(), xa.ell = dell.d(), xa.X = dX.d();
+    xa.gp = ggp.d(), xa.gc = ggc.d();
+    launch_qf_xgrad(xa, st);
+    launch_qf_xgrad_combine(ggp.d(), ggc.d(), n, n, Q, Df, P, dW.d(), gdm.d(), gdv.d(), st);
+    HIP_TRY(hipGetLastError());
+    if (m) HIP_TRY(hipMemcpyAsync(m + r0 * Df, dm.p, sizeof(double) * n * Df, hipMemcpyDeviceToHost, st));
+    if (v) HIP_TRY(hipMemcpyAsync(v + r0 * Df, dv.p, sizeof(double) * n * Df, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(dm_out + r0 * Df * P, gdm.p, sizeof(double) * n * Df * P, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(dv_out + r0 * Df * P, gdv.p, sizeof(double) * n * Df * P, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (dX is reused by the next chunk's upload)
+  }
+}

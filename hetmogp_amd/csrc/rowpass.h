@@ -173,6 +173,21 @@ void launch_joint_normal(unsigned long long seed, int S, long long n, double* Z,
 // mean[j * N + i] = m[i * Df + d[j]]: the joint vector's function-major mean out of q(f)'s [N][Df] rows (i0: first row of the chunk)
 void launch_joint_gather(const double* m, int Df, const int* d, int nD, long long N, long long i0, long long nrows, double* mean,
                          hipStream_t s);
+// Gradients of q(f) with respect to the new inputs (xgrad.hip): gp[q][i][j] = (1 / l_q^2) sum_m a_qm A_q[i][m] (z_qmj - x_ij),
+// gc[q][i][j] = (2 / l_q^2) sum_m T_q[i][m] A_q[i][m] (z_qmj - x_ij) for the n rows of one chunk.  A, T: [Q][sK], n x M row-major (lda = M);
+// Z: latent q's inducing inputs at Z + q P, row stride ldz; a: [Q][M]; ell: [Q]; X: [n][P]; gp, gc: [Q][ldo][P].  Every pointer is device
+// memory.  A wave owns a few rows and shares nothing between them but the loaded a and z: a row's bits depend on that row's own inputs alone.
+struct XgradArgs {
+  int P = 1, Q = 1, M = 0, ldz = 0;
+  long long n = 0, sK = 0, ldo = 0;
+  const double *A = nullptr, *T = nullptr, *Z = nullptr, *a = nullptr, *ell = nullptr, *X = nullptr;
+  double *gp = nullptr, *gc = nullptr;
+  int vec = 0;                     // (set by the launcher: M even and the rows 16-byte aligned)
+};
+void launch_qf_xgrad(const XgradArgs& a, hipStream_t s);
+// dm[i][d][j] = sum_q W_qd gp[q][i][j], dv[i][d][j] = sum_q W_qd^2 gc[q][i][j] (q from left to right); W: [Q][Df]; dm, dv: [n][Df][P]
+void launch_qf_xgrad_combine(const double* gp, const double* gc, long long ldo, long long n, int Q, int Df, int P, const double* W,
+                             double* dm, double* dv, hipStream_t s);
 // K[n][m] = var * exp(-r2/2); X rows have stride ldx, Z rows stride ldz (block q of the M x Q*P inducing array)
 void launch_rbf(const double* X, int ldx, long long N, int P, const double* Z, int ldz, int M, double var, double ell,
                 double* K, bool same, hipStream_t s, const int* rowwin = nullptr, bool exact = true,

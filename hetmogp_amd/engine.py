@@ -412,6 +412,19 @@ class Engine(object):
             return F, dict(mean=mean, L=L, jitter=float(jit.value), rung=int(rung.value))
         return F
 
+    def predict_f_grad(self, Xnew, return_mv=False):
+        """Gradients of q(f) with respect to the inputs Xnew: (dm (N, Df, P), dv (N, Df, P)), dm[i, d, j] = d m_d / d x_j and
+        dv[i, d, j] = d v_d / d x_j at row i, in the mode of the evaluation they are taken from.  v is the SIGNED variance `predict_f`
+        returns (before any abs).  return_mv=True: (m, v, dm, dv) with m, v the bits of `predict_f`."""
+        Xnew = _f64(Xnew).reshape(-1, self.P)
+        N = Xnew.shape[0]
+        dm, dv = np.zeros((N, self.Df, self.P)), np.zeros((N, self.Df, self.P))
+        m = np.zeros((N, self.Df)) if return_mv else None
+        v = np.zeros((N, self.Df)) if return_mv else None
+        check(lib.hmogp_predict_f_grad(self._h, _p(Xnew), N, _p(m) if return_mv else None, _p(v) if return_mv else None, _p(dm), _p(dv)),
+              self._h)
+        return (m, v, dm, dv) if return_mv else (dm, dv)
+
     # ------------------------------------------------------------------------------------------ resident q(u)
     def qu_load(self, m_u, L_flat):
         m_u, L_flat = _f64(m_u).reshape(self.M, self.Q), _f64(L_flat).reshape(self.Mtri, self.Q)
@@ -783,3 +796,30 @@ def select_inducing_rows(X, variance, lengthscale, Mmax, tol=0.0, forced=None, r
     if return_factor:
         out.update(L=L, d=d)
     return out
+
+
+def qf_input_grad_rows(X, Z, variance, lengthscale, a, C, W, exact=True, device=None):
+    """Gradients of q(f) with respect to the inputs, from explicit coefficients (`hmogp_qf_input_grad`).  X (N, P); Z (M, Q P)
+    laid out as the engine's Z (latent q's inducing inputs in columns q P .. q P + P); variance, lengthscale (Q,); a (Q, M); C (Q, M, M);
+    W (Q, Df).  With k_qm = variance_q exp(-|x - z_qm|^2 / 2 l_q^2), p_q = sum_m a_qm k_qm, c_q = sum_mm' k_qm C_q,mm' k_qm',
+    m_d = sum_q W_qd p_q and v_d = const + sum_q W_qd^2 c_q: returns (dm, dv), both (N, Df, P), dm[i, d, j] = d m_d / d x_j and
+    dv[i, d, j] = d v_d / d x_j (of the signed v: no abs anywhere).  exact: the rounding variant of `rbf_cross_cov`.  A row's result
+    depends on that row alone, bit for bit."""
+    device = _resolve_device(device)
+    X = _f64(X)
+    X = X.reshape(X.shape[0], -1) if X.ndim != 2 else X
+    N, P = X.shape
+    var, ell = _f64(np.atleast_1d(variance)).ravel(), _f64(np.atleast_1d(lengthscale)).ravel()
+    Q = var.shape[0]
+    a, W = _f64(a), _f64(W)
+    a = a.reshape(Q, -1) if a.ndim != 2 else a
+    W = W.reshape(Q, -1) if W.ndim != 2 else W
+    M, Df = a.shape[1], W.shape[1]
+    Z, C_ = _f64(Z), _f64(C)
+    if ell.shape != var.shape or a.shape[0] != Q or W.shape[0] != Q or Z.shape != (M, Q * P) or C_.shape != (Q, M, M):
+        raise _lib.InvalidArgument("qf_input_grad_rows: shapes must be X (N, P), Z (M, Q P), variance / lengthscale (Q,), a (Q, M), "
+                                   "C (Q, M, M), W (Q, Df)")
+    dm, dv = np.zeros((N, Df, P)), np.zeros((N, Df, P))
+    check(lib.hmogp_qf_input_grad(device, N, P, _p(X), M, Q, _p(Z), _p(var), _p(ell), 1 if exact else 0, _p(a), _p(C_), Df, _p(W),
+                                  _p(dm), _p(dv)))
+    return dm, dv

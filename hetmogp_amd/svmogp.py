@@ -843,6 +843,34 @@ class SVMOGP(object):
         mean, cov = self._engine.predict_f_joint(Xnew, functions)
         return np.ascontiguousarray(mean.T), cov
 
+    def _grad_functions(self, functions):
+        if functions is None:
+            return list(range(self.num_output_funcs))
+        d = [int(f) for f in np.ravel(functions)]
+        if any(f < 0 or f >= self.num_output_funcs for f in d):
+            raise ValueError("functions: indices must lie in 0 .. %d" % (self.num_output_funcs - 1))
+        return d
+
+    def predictive_gradients(self, Xnew, functions=None):
+        """Gradients of q(f) with respect to the inputs (GPy's `predictive_gradients`, at the level of the latent parameter functions;
+        DESIGN 9t): (dm (N, nD, P), dv (N, nD, P)), dm[i, j, p] = d m_d / d x_p and dv[i, j, p] = d v_d / d x_p of function d =
+        functions[j] at row i -- the local effect of input p on, e.g., a Poisson task's log-rate or a Bernoulli task's logit.
+        functions=None: all Df functions; a list selects and orders them.  v is the SIGNED variance the engine's `predict_f` returns:
+        the gradient is taken before any abs (`predictive_new` applies one)."""
+        self._refresh()
+        d = self._grad_functions(functions)
+        dm, dv = self._engine.predict_f_grad(np.asarray(Xnew, dtype=float).reshape(-1, self.Xdim))
+        return np.ascontiguousarray(dm[:, d, :]), np.ascontiguousarray(dv[:, d, :])
+
+    def input_sensitivity(self, X=None, functions=None):
+        """Relevance of every input dimension for every function (the kernels are isotropic: there are no ARD lengthscales to read):
+        (nD, P), the root mean square over the rows of X of d m_d / d x_p (`predictive_gradients`).  X=None: the model's pooled training
+        inputs of all tasks."""
+        if X is None:
+            X = np.concatenate(self.Xmulti_all, 0)
+        dm, _ = self.predictive_gradients(X, functions)
+        return np.sqrt(np.mean(dm * dm, axis=0))
+
     def _joint_seed(self, seed):
         if seed is None:       # (as `_Lik.samples`: one draw from NumPy's GLOBAL generator)
             seed = int(np.random.randint(0, 2 ** 31 - 1))

@@ -592,6 +592,35 @@ int hmogp_select_inducing(int32_t device, int64_t N, int32_t P, const double* X 
                           double* dpiv /* [Mmax] */, double* trace /* [Mmax + 1] */, double* L /* [N, Mmax] or NULL */,
                           double* d /* [N] or NULL */, int32_t* Mout);
 
+/* Gradients of q(f) with respect to the new inputs (GPy's `predictive_gradients` at the level of the latent functions).
+ * hmogp_predict_f forms, for row x, latent q and function d,
+ *   k_qm(x) = variance_q exp(-r_qm^2 / 2 l_q^2),  p_q = sum_m a_qm k_qm,  c_q = sum_mm' k_qm C_q,mm' k_qm',
+ *   m_d = sum_q W_qd p_q,  v_d = sum_q (W_qd^2 + kappa_qd) variance_q + W_qd^2 c_q
+ * with a_q = Kuu^-1 m_q (hmogp_posterior_u's woodbury_vector) and C_q = Kuu^-1 S_q Kuu^-1 - Kuu^-1 (the NEGATIVE of its woodbury_inv).
+ * The prior term of v_d is constant in x (the kernel is stationary), so with t_q = one row of A_q C_q, A_q = k_q(X, Z_q):
+ *   gp_qj = (1 / l_q^2) sum_m a_qm k_qm (z_qmj - x_j),   gc_qj = (2 / l_q^2) sum_m t_qm k_qm (z_qmj - x_j),
+ *   dm[i, d, j] = d m_d / d x_j = sum_q W_qd gp_qj,      dv[i, d, j] = d v_d / d x_j = sum_q W_qd^2 gc_qj.
+ * v is the SIGNED value hmogp_predict_f returns: the gradient is that of v before any abs a caller takes.  (z - x) is one subtraction
+ * per term; k_qm is the image the mean is formed with (written by the K_uf kernel in the named rounding variant and read back); a row's
+ * result depends on that row's own inputs alone -- not on N, the row's position, or any chunking: the same row gives the same bits.
+ * hmogp_qf_input_grad is the building block: any a [Q, M] and any C [Q, M, M] (t_q = k_q^T C_q: C_q,m'm weights k_qm'), `exact` the
+ * rounding variant of hmogp_rbf_cross_cov_ex, Z laid out as in hmogp_params ([M, Q P]: latent q's inputs in columns q P .. q P + P).
+ * HMOGP_E_INVALID, with a message that names the argument and before the device is touched, for N < 0, P outside 1..4, M, Q or Df below 1,
+ * Q above 8, a required pointer NULL with N > 0, a variance or lengthscale that is not finite and > 0; then HMOGP_E_NO_DEVICE without a
+ * device.  N = 0 returns success at once.
+ * hmogp_predict_f_grad is the engine path, from the parameters of the last evaluation and in ITS mode (default: T = A C_q with the explicit
+ * C_q; strict: T = ((A Kuu^-1) L_q L_q^T - A) Kuu^-1 through row solves against Luu, C_q never read), small or regular model, in the chunks
+ * of hmogp_predict_f.  m and v (each may be NULL) are hmogp_predict_f's own values, bit for bit.  HMOGP_E_INVALID for a NULL handle,
+ * Nnew < 0, or Xnew, dm or dv NULL with Nnew > 0; HMOGP_E_STATE before the first evaluation; Nnew = 0 returns success at once.
+ * New symbols only: ABI version 8 stays.                                                                                              */
+int hmogp_qf_input_grad(int32_t device, int64_t N, int32_t P, const double* X /* [N, P] */, int32_t M, int32_t Q,
+                        const double* Z /* [M, Q*P], as hmogp_params */, const double* variance /* [Q] */,
+                        const double* lengthscale /* [Q] */, int32_t exact /* the rbf rounding variant, as hmogp_rbf_cross_cov_ex */,
+                        const double* a /* [Q, M] */, const double* C /* [Q, M, M] */, int32_t Df, const double* W /* [Q, Df] */,
+                        double* dm /* [N, Df, P] */, double* dv /* [N, Df, P] */);
+int hmogp_predict_f_grad(hmogp_handle h, const double* Xnew, int64_t Nnew, double* m /* [Nnew, Df] or NULL */,
+                         double* v /* [Nnew, Df] or NULL */, double* dm /* [Nnew, Df, P] */, double* dv /* [Nnew, Df, P] */);
+
 /* Data generation on the device: one draw Y[n] ~ p(y | F[n, :]) per row with the link functions and clips of the
  * reference's `<likelihood>.samples` (het_likelihood.py:72-83 -> e.g. gamma.py:43-50, categorical.py:65-75; labels of
  * Categorical are 1..K).  Counter-based generator keyed by (seed, row): reproducible, but a different stream than

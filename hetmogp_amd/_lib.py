@@ -118,6 +118,8 @@ EXPORTS = {
                                       C.c_double, c_double_p]),
     "hmogp_rbf_cross_cov_ex": (C.c_int, [C.c_int32, c_double_p, C.c_int64, c_double_p, C.c_int32, C.c_int32, C.c_double,
                                          C.c_double, C.c_int32, c_double_p]),
+    "hmogp_kuf_windows": (C.c_int, [C.c_int32, c_double_p, C.c_int64, C.c_int32, c_double_p, C.c_int32, C.c_int32, C.c_double,
+                                    c_int32_p, c_int32_p]),
     "hmogp_qu_load": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "hmogp_qu_read": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "hmogp_qu_adadelta": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),

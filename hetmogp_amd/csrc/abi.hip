@@ -372,6 +372,32 @@ int hmogp_rbf_cross_cov_ex(int32_t device, const double* X, int64_t N, const dou
   });
 }
 
+// The exact-zero windows of one (row range, latent) as the engine's windows mode computes them: launch_windows as it stands, the two
+// integer tables copied back.  Stateless: no engine, no workspace.  Every refusal sits in front of need_device.
+int hmogp_kuf_windows(int32_t device, const double* X, int64_t N, int32_t P, const double* Z, int32_t ldz, int32_t M, double lengthscale,
+                      int32_t* rowwin, int32_t* colwin) {
+  return guarded(nullptr, [&] {
+    auto refuse = [](const char* what) { throw EngineError{HMOGP_E_INVALID, std::string("hmogp_kuf_windows: ") + what}; };
+    if (N < 1 || N > 0x7fffff80LL) refuse("N must be in 1..2^31 - 128");
+    if (P < 1 || P > 4) refuse("P must be in 1..4");
+    if (M < 1 || M > 8192) refuse("M must be in 1..8192");
+    if (ldz < P) refuse("ldz must be >= P");
+    if (!X || !Z || !rowwin || !colwin) refuse("a pointer is NULL");
+    need_device(device);
+    const long long tiles = (N + 127) / 128, nz = (long long)(M - 1) * ldz + P;
+    const int ncb = (M + 127) / 128;
+    DevBuf dX, dZ, dR, dC, dH;
+    dX.ensure(sizeof(double) * N * P), dZ.ensure(sizeof(double) * nz);
+    dR.ensure(sizeof(int) * 2 * tiles), dC.ensure(sizeof(int) * 2 * ncb), dH.ensure((size_t)tiles * ncb);
+    HIP_TRY(hipMemcpy(dX.p, X, sizeof(double) * N * P, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dZ.p, Z, sizeof(double) * nz, hipMemcpyHostToDevice));
+    launch_windows(dX.d(), N, P, dZ.d(), ldz, M, lengthscale, dR.as<int>(), dC.as<int>(), dH.as<unsigned char>(), nullptr);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(rowwin, dR.p, sizeof(int) * 2 * tiles, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(colwin, dC.p, sizeof(int) * 2 * ncb, hipMemcpyDeviceToHost));
+  });
+}
+
 int hmogp_select_inducing(int32_t device, int64_t N, int32_t P, const double* X, int32_t Q, const double* variance,
                           const double* lengthscale, int32_t Mmax, double tol, int32_t n_forced, const int64_t* forced, int64_t* pivots,
                           double* Z, double* dpiv, double* trace, double* L, double* d, int32_t* Mout) {

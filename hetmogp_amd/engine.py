@@ -605,6 +605,21 @@ def rbf_cross_cov(X, Z, variance, lengthscale, device=None, exact=True):
     return K
 
 
+def kuf_windows_rows(X, Z, lengthscale, device=None):
+    """The exact-zero windows of k(X, Z) as the engine's windows mode computes them for one row range and one latent
+    (hmogp_kuf_windows): (rowwin [ceil(N / 128), 2], colwin [ceil(M / 128), 2]), int32."""
+    device = _resolve_device(device)
+    X, Z = _f64(X), _f64(Z)
+    X = X if X.ndim == 2 else X.reshape(X.shape[0], -1)
+    Z = Z if Z.ndim == 2 else Z.reshape(Z.shape[0], -1)
+    N, M, P = X.shape[0], Z.shape[0], X.shape[1]
+    rowwin = np.zeros(((N + 127) // 128, 2), dtype=np.int32)
+    colwin = np.zeros(((M + 127) // 128, 2), dtype=np.int32)
+    check(lib.hmogp_kuf_windows(device, _p(X), N, P, _p(Z), Z.shape[1], M, float(lengthscale), rowwin.ctypes.data_as(_lib.c_int32_p),
+                                colwin.ctypes.data_as(_lib.c_int32_p)))
+    return rowwin, colwin
+
+
 def jitchol_inv(A, forced_rung=None, device=None):
     device = _resolve_device(device)
     A = _f64(A)

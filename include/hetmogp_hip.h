@@ -407,6 +407,16 @@ int hmogp_rbf_cross_cov(int32_t device, const double* X, int64_t N, const double
  * <= 2 ulp of the exponent away).                                                                                 */
 int hmogp_rbf_cross_cov_ex(int32_t device, const double* X, int64_t N, const double* Z, int32_t M, int32_t P,
                            double variance, double lengthscale, int32_t exact, double* K /* [N, M] */);
+/* The exact-zero windows of K = k(X, Z) exactly as HMOGP_CFG_EXACT_ZERO_WINDOWS computes them for one row range and one latent
+ * (a stateless view of the engine's own window kernels; still ABI v8).  X [N, P] row-major, Z [M, ldz] with the latent's inputs in
+ * its first P columns (ldz >= P: pass hmogp_params.Z + q P with ldz = Q P), 1 <= M <= 8192, 1 <= P <= 4.
+ *   rowwin [ceil(N / 128)][2]  per 128-row tile the column range [lo, hi) outside which every K[n][m] of the tile is exactly 0.0;
+ *                              lo, hi multiples of 16, hi <= (M + 15) & ~15 (which may exceed M); [0, 0) = the tile has no non-zero
+ *   colwin [ceil(M / 128)][2]  per 128-column block the row range [lo, hi) that holds the tiles touching it; [0, 0) = none
+ * Inputs that are not banded (a tile inside a block's row range that does not touch the block) give the full ranges [0, (M+15)&~15)
+ * and [0, N) everywhere.                                                                                                          */
+int hmogp_kuf_windows(int32_t device, const double* X, int64_t N, int32_t P, const double* Z, int32_t ldz, int32_t M,
+                      double lengthscale, int32_t* rowwin, int32_t* colwin);
 /* Batched lower Cholesky with GPy's jitter ladder + inverse: A [Q,M,M] -> L, Ainv; rung[q] as above.     */
 int hmogp_jitchol_inv(int32_t device, const double* A, int32_t Q, int32_t M, const int32_t* forced_rung,
                       double* L, double* Ainv, int32_t* rung);

@@ -27,6 +27,7 @@ LIK_IDS_BY_NAME = dict(Gaussian=0, Bernoulli=1, HetGaussian=2, Categorical=3, Po
                        Student=8, Ordinal=9, Dirichlet=10, NegBinomial=11, Weibull=12, Binomial=13, BetaBinomial=14,
                        ZIPoisson=15)
 JOINT_MAXDIM = 8192     # largest joint dimension nD * N of hmogp_predict_f_joint / hmogp_sample_f_joint
+PATHS_MAXFEAT, PATHS_MAXCOLS, PATHS_MAXSETS = 8192, 4096, 16   # hmogp_paths_*: most frequencies Lf, most columns nD * S, live sets per engine
 ZSEL_FLOOR = 2.0 ** -40  # HMOGP_ZSEL_FLOOR: d / k0 at or below which hmogp_select_inducing stops, whatever tol
 QUANT_MAXP = 8          # most probabilities per hmogp_predictive_quantile / hmogp_predict_quantile call
 E_INVALID, E_NO_DEVICE, E_NOT_PD, E_SQI_UNSTABLE, E_STATE, E_COMM = -1, -2, -3, -4, -5, -6
@@ -161,6 +162,10 @@ EXPORTS = {
     "hmogp_qf_input_grad": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p,
                                       C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p]),
     "hmogp_predict_f_grad": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hmogp_paths_create": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_uint64, c_int32_p]),
+    "hmogp_paths_eval": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_double_p]),
+    "hmogp_paths_state": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hmogp_paths_free": (C.c_int, [C.c_void_p, C.c_int32]),
     "hmogp_sample": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint64, c_double_p, c_double_p]),
     "hmogp_bench_contraction": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, c_double_p]),
     "hmogp_host_alloc": (C.c_void_p, [C.c_uint64]),

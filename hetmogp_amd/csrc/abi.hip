@@ -342,6 +342,27 @@ int hmogp_predict_f_grad(hmogp_handle h, const double* Xnew, int64_t Nnew, doubl
   return guarded(h, [&] { h->predict_f_grad(Xnew, Nnew, m, v, dm, dv); });
 }
 
+// pathwise posterior samples -- a NULL handle is refused with a message, like hmogp_predict_f_grad's
+static int paths_no_handle(const char* who) {
+  return guarded(nullptr, [&] { throw EngineError{HMOGP_E_INVALID, std::string(who) + ": the handle is NULL"}; });
+}
+int hmogp_paths_create(hmogp_handle h, int32_t nD, const int32_t* d_index, int32_t S, int32_t Lf, uint64_t seed, int32_t* id) {
+  if (!h) return paths_no_handle("hmogp_paths_create");
+  return guarded(h, [&] { h->paths_create(nD, d_index, S, Lf, seed, id); });
+}
+int hmogp_paths_eval(hmogp_handle h, int32_t id, const double* Xnew, int64_t Nnew, double* F) {
+  if (!h) return paths_no_handle("hmogp_paths_eval");
+  return guarded(h, [&] { h->paths_eval(id, Xnew, Nnew, F); });
+}
+int hmogp_paths_state(hmogp_handle h, int32_t id, double* omega, double* theta, double* v, double* u) {
+  if (!h) return paths_no_handle("hmogp_paths_state");
+  return guarded(h, [&] { h->paths_state(id, omega, theta, v, u); });
+}
+int hmogp_paths_free(hmogp_handle h, int32_t id) {
+  if (!h) return paths_no_handle("hmogp_paths_free");
+  return guarded(h, [&] { h->paths_free(id); });
+}
+
 int hmogp_last_timings(hmogp_handle h, double* out_ms, int64_t* launches) {
   if (!h || !out_ms) return HMOGP_E_INVALID;
   for (int c = 0; c < NCAT; ++c) {

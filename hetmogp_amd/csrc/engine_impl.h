@@ -569,6 +569,27 @@ struct hmogp_engine {
   // d m_d / d x_j and d v_d / d x_j (v the signed value predict_f returns) at Xnew, dm / dv [Nnew][Df][P]; m, v (either may
   // be null) are qf_chunk's own: the bits of predict_f
   void predict_f_grad(const double* Xnew, long long Nnew, double* m, double* v, double* dm, double* dv);
+  // pathwise (Matheron) posterior samples.  A path set is a snapshot: its own copies of everything an evaluation reads.
+  struct PathSet {
+    bool live = false;
+    int nD = 0, S = 0, Lf = 0;
+    unsigned long long seed = 0;
+    DevBuf Z, omega, cq, var, ell, Theta, V, u;   // Z [M][Q P] | [Q][Lf][P] | [Q] | [Q] | [Q] | [Q][2 Lf][S nD] | [Q][M][S nD] | [Q][S][M]
+    void reset() {
+      for (DevBuf* b : {&Z, &omega, &cq, &var, &ell, &Theta, &V, &u}) b->release();
+      live = false;
+    }
+  };
+  PathSet path_sets[HMOGP_PATHS_MAXSETS];
+  DevBuf paths_wX, paths_wPhi, paths_wA, paths_wF;   // chunk workspace of paths_eval (X, Phi, A_q, F): grows as needed, released with the last live set
+  // rows per chunk of an evaluation: the feature workspace Phi [Q][rows][2 Lf] of one chunk stays within this many bytes (1 GiB; so do
+  // A_q and the chunk of F, each).  The products are one 128-row tile of S nD columns wide: the chunk's rows are what fills the device
+  static constexpr long long PATHS_PHI_BUDGET = 1LL << 30;
+  PathSet& path_set(int id);    // HMOGP_E_INVALID for an unknown or freed id
+  void paths_create(int nD, const int* d, int S, int Lf, unsigned long long seed, int* id);
+  void paths_eval(int id, const double* Xnew, long long Nnew, double* F);
+  void paths_state(int id, double* omega, double* theta, double* v, double* u);
+  void paths_free(int id);
 
   // ---- likelihood parameters (lik_param.hip) ----
   bool lik_grad_on = false;      // hmogp_lik_grad_enable: persistent

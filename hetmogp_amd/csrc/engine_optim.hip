@@ -517,3 +517,213 @@ void hmogp_engine::predict_f_grad(const double* Xnew, long long Nnew, double* m,
     HIP_TRY(hipStreamSynchronize(st));   // (dX is reused by the next chunk's upload)
   }
 }
+
+// pathwise (Matheron) posterior samples.  A path set is drawn ONCE from the parameters of the last evaluation -- q(u_q) =
+// N(m_q, L_q L_q^T) in dmu / L, K_q = k_q(Z_q, Z_q) from Z and the kernel parameters -- and is a snapshot:
+//   omega = zeta / (pi ell_q); theta, eps; u = m_q + eps L_q^T (ONE b_tri product onto the mean); Phi_Z = Phi_q(Z_q) by the feature kernel;
+//   R = u - theta Phi_Z^T; v = R K_q^-1 by the row solves against the set's OWN factor of K_q; Theta~ = w theta + sqrt(kappa) theta', V~ = w v.
+// One set of bits whatever mode the evaluation ran in.  (a) The factor is NOT the engine's Luu buffer: an M <= 64 evaluation in the default
+// mode leaves the factor of the fused small-model kernel there, a strict one the blocked potrf's -- both valid, not the same last bits.
+// The set forms K_q itself (launch_rbf with the arguments u_algebra passes) and factorises it with jitchol_batched forced onto the rung
+// the evaluation took: the regular kernels' factor of the same matrix on every path, O(Q M^3 / 3) once per set.  (b) The solve is
+// potrs_rows_inplace WITHOUT a mirrored factor and pivots' reciprocals: the blocked substitution kernels whatever S is (no strict-mode
+// workspace is read).  Every product is the existing GEMM accumulating into its target (beta = 1): the general FP64-MFMA kernel
+// whatever the shape.  Every refusal comes before the first device call, each memory question before the allocation it is about.
+hmogp_engine::PathSet& hmogp_engine::path_set(int id) {
+  if (id < 0 || id >= HMOGP_PATHS_MAXSETS || !path_sets[id].live) throw EngineError{HMOGP_E_INVALID, "paths: unknown or freed path-set id"};
+  return path_sets[id];
+}
+
+void hmogp_engine::paths_create(int nD, const int* d, int S, int Lf, unsigned long long seed, int* id) {
+  if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to draw paths from"};
+  if (nD < 1 || !d) throw EngineError{HMOGP_E_INVALID, "paths: nD must be >= 1 and d_index given"};
+  {
+    std::vector<char> seen((size_t)Df, 0);
+    for (int j = 0; j < nD; ++j) {
+      if (d[j] < 0 || d[j] >= Df) throw EngineError{HMOGP_E_INVALID, "paths: a function index is out of range"};
+      if (seen[d[j]]) throw EngineError{HMOGP_E_INVALID, "paths: a function index is repeated"};
+      seen[d[j]] = 1;
+    }
+  }
+  if (S < 1) throw EngineError{HMOGP_E_INVALID, "paths: S must be >= 1"};
+  if (Lf < 1) throw EngineError{HMOGP_E_INVALID, "paths: Lf must be >= 1"};
+  if (Lf > HMOGP_PATHS_MAXFEAT) throw EngineError{HMOGP_E_INVALID, "paths: Lf exceeds HMOGP_PATHS_MAXFEAT"};
+  if ((long long)nD * S > HMOGP_PATHS_MAXCOLS) throw EngineError{HMOGP_E_INVALID, "paths: nD * S exceeds HMOGP_PATHS_MAXCOLS"};
+  if (!id) throw EngineError{HMOGP_E_INVALID, "paths: id is NULL"};
+  int slot = -1;
+  for (int i = 0; i < HMOGP_PATHS_MAXSETS && slot < 0; ++i)
+    if (!path_sets[i].live) slot = i;
+  if (slot < 0) throw EngineError{HMOGP_E_INVALID, "paths: no free slot (HMOGP_PATHS_MAXSETS live path sets)"};
+
+  HIP_TRY(hipSetDevice(device));
+  const long long K2 = 2LL * Lf, nc = (long long)nD * S, MM = (long long)M * M, sU = (long long)S * M;
+  const long long nZ = (long long)M * Q * P;
+  {   // the memory question: the set's state and the draw's workspace, before any allocation
+    const double state = 8.0 * ((double)nZ + (double)Q * Lf * P + 3.0 * Q + (double)Q * K2 * nc + (double)Q * M * nc + (double)Q * sU);
+    const double work = 8.0 * ((double)Q * S * K2 + 2.0 * Q * sU + (double)Q * M * K2 + 3.0 * Q * MM + 2.0 * Q * nD + HMOGP_MAXQ) + 4.0 * (nD + HMOGP_MAXQ);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (state + work > (double)free_b) {
+      char buf[256];
+      std::snprintf(buf, sizeof buf, "paths: the set's state (%.0f bytes) and the draw's workspace (%.0f bytes) need %.0f bytes, the device has %.0f free",
+                    state, work, state + work, (double)free_b);
+      throw EngineError{HMOGP_E_INVALID, buf};
+    }
+  }
+  PathSet& ps = path_sets[slot];
+  ps.nD = nD, ps.S = S, ps.Lf = Lf, ps.seed = seed;
+  try {
+  ps.Z.ensure(sizeof(double) * nZ), ps.omega.ensure(sizeof(double) * Q * Lf * P);
+  ps.cq.ensure(sizeof(double) * Q), ps.var.ensure(sizeof(double) * Q), ps.ell.ensure(sizeof(double) * Q);
+  ps.Theta.ensure(sizeof(double) * Q * K2 * nc), ps.V.ensure(sizeof(double) * Q * M * nc), ps.u.ensure(sizeof(double) * Q * sU);
+  DevBuf dd, dws, dth, deps, dR, dPZ, pK, pLuu, pscr, pinfo, pjit;
+  pK.ensure(sizeof(double) * Q * MM), pLuu.ensure(sizeof(double) * Q * MM, true), pscr.ensure(sizeof(double) * Q * MM);
+  pinfo.ensure(sizeof(int) * HMOGP_MAXQ), pjit.ensure(sizeof(double) * HMOGP_MAXQ);
+  dd.ensure(sizeof(int) * nD), dws.ensure(sizeof(double) * 2 * Q * nD);
+  dth.ensure(sizeof(double) * Q * S * K2), deps.ensure(sizeof(double) * Q * sU), dR.ensure(sizeof(double) * Q * sU);
+  dPZ.ensure(sizeof(double) * Q * M * K2);
+  std::vector<double> hc((size_t)Q), hws((size_t)2 * Q * nD);
+  for (int q = 0; q < Q; ++q) {
+    hc[q] = std::sqrt(h_var[q] / (double)Lf);
+    for (int j = 0; j < nD; ++j) {
+      hws[(size_t)q * nD + j] = h_W[(size_t)q * Df + d[j]];
+      hws[(size_t)(Q + q) * nD + j] = std::sqrt(h_kap[(size_t)q * Df + d[j]]);
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(dd.p, d, sizeof(int) * nD, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dws.p, hws.data(), sizeof(double) * 2 * Q * nD, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ps.cq.p, hc.data(), sizeof(double) * Q, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ps.var.p, h_var.data(), sizeof(double) * Q, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ps.ell.p, h_ell.data(), sizeof(double) * Q, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ps.Z.p, dZ.p, sizeof(double) * nZ, hipMemcpyDeviceToDevice, st));
+  launch_paths_draw(seed, Q, P, Lf, S, M, ps.ell.d(), dmu.d(), ps.omega.d(), dth.d(), deps.d(), ps.u.d(), st);
+  {   // u[q][s][:] = m_q + L_q eps[q][s][:]: op(B)[k][j] = L_q[j][k], zero for k > j
+    GemmArgs g;
+    g.A = deps.d(), g.lda = M, g.a_kmajor = 0, g.sA = sU;
+    g.B = L.d(), g.ldb = M, g.b_kmajor = 0, g.sB = MM, g.b_tri = -1;
+    g.C = ps.u.d(), g.ldc = M, g.sC = sU;
+    g.M = S, g.N = M, g.K = M;
+    g.nbatch = Q;
+    g.alpha = 1.0, g.beta = 1.0;
+    launch_gemm_f64(g, st);
+  }
+  PathsArgs fa;
+  fa.P = P, fa.Q = Q, fa.Lf = Lf, fa.ldx = Q * P, fa.rows = M, fa.sX = P;
+  fa.X = ps.Z.d(), fa.omega = ps.omega.d(), fa.cq = ps.cq.d(), fa.Phi = dPZ.d();
+  launch_paths_features(fa, st);                                              // Phi_q(Z_q): [Q][M][2 Lf]
+  HIP_TRY(hipMemcpyAsync(dR.p, ps.u.p, sizeof(double) * Q * sU, hipMemcpyDeviceToDevice, st));
+  {   // R = u - theta Phi_Z^T: op(B)[k][m] = Phi_Z[m][k]
+    GemmArgs g;
+    g.A = dth.d(), g.lda = (int)K2, g.a_kmajor = 0, g.sA = (long long)S * K2;
+    g.B = dPZ.d(), g.ldb = (int)K2, g.b_kmajor = 0, g.sB = (long long)M * K2;
+    g.C = dR.d(), g.ldc = M, g.sC = sU;
+    g.M = S, g.N = M, g.K = (int)K2;
+    g.nbatch = Q;
+    g.alpha = -1.0, g.beta = 1.0;
+    launch_gemm_f64(g, st);
+  }
+  {   // the set's own factor of K_q (see above): K_uu as u_algebra builds it, the blocked potrf on the rung the evaluation took
+    RbfBatch kb;
+    kb.nq = Q, kb.var = ps.var.d(), kb.ell = ps.ell.d(), kb.sZ = P, kb.sX = P, kb.sK = MM;
+    launch_rbf(ps.Z.d(), Q * P, M, P, ps.Z.d(), Q * P, M, 0.0, 1.0, pK.d(), false, st, nullptr, true, &kb);
+    std::vector<int> r(rung.begin(), rung.end());
+    r.resize((size_t)Q, -1);
+    jitchol_batched(pK.d(), pLuu.d(), Q, M, h_var.data(), r.data(), pinfo.as<int>(), pjit.d(), pscr.d(), st);
+  }
+  potrs_rows_inplace(dR.d(), sU, pLuu.d(), MM, M, S, Q, st);                   // v = R K_q^-1, in place, the rows as right-hand sides
+  launch_paths_scale(seed, Q, Lf, S, M, nD, dd.as<int>(), dws.d(), dws.d() + (long long)Q * nD, dth.d(), dR.d(), ps.Theta.d(), ps.V.d(), st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));   // (the workspace and the host vectors go out of scope)
+  } catch (...) {
+    (void)hipStreamSynchronize(st);
+    ps.reset();
+    throw;
+  }
+  ps.live = true;
+  *id = slot;
+}
+
+void hmogp_engine::paths_eval(int id, const double* Xnew, long long Nnew, double* F) {
+  if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to draw paths from"};
+  PathSet& ps = path_set(id);
+  if (Nnew < 0) throw EngineError{HMOGP_E_INVALID, "paths: Nnew must be >= 0"};
+  if (Nnew > 0 && (!Xnew || !F)) throw EngineError{HMOGP_E_INVALID, "paths: Xnew and F must be given"};
+  if (Nnew == 0) return;
+
+  HIP_TRY(hipSetDevice(device));
+  const int Lf = ps.Lf;
+  const long long K2 = 2LL * Lf, nc = (long long)ps.nD * ps.S;
+  // rows per chunk: Phi [Q][rows][2 Lf] of one chunk within PATHS_PHI_BUDGET, and so A [Q][rows][M] and F [S nD][rows] each (a multiple
+  // of 128 rows, at least 128), at most the engine's chunk_rows
+  const long long widest = std::max<long long>(std::max<long long>(Q * K2, (long long)Q * M), nc);
+  long long rows = std::max<long long>(128, PATHS_PHI_BUDGET / (8 * widest) / 128 * 128);
+  rows = std::min(std::min(rows, chunk), std::min<long long>(Nnew, 1LL << 20));
+  // the chunk workspace stays with the engine (released with the last live set) and only grows: the memory question is about the growth
+  DevBuf &pX = paths_wX, &pPhi = paths_wPhi, &pA = paths_wA, &pF = paths_wF;
+  const size_t want[4] = {sizeof(double) * rows * P, sizeof(double) * Q * rows * K2, sizeof(double) * Q * rows * M, sizeof(double) * nc * rows};
+  DevBuf* const ws[4] = {&pX, &pPhi, &pA, &pF};
+  double grow = 0.0;
+  for (int i = 0; i < 4; ++i)
+    if (want[i] > ws[i]->bytes) grow += (double)want[i] - (double)ws[i]->bytes;
+  if (grow > 0.0) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (grow > (double)free_b) {
+      char buf[256];
+      std::snprintf(buf, sizeof buf, "paths: the evaluation's chunk workspace needs %.0f more bytes, the device has %.0f free", grow, (double)free_b);
+      throw EngineError{HMOGP_E_INVALID, buf};
+    }
+  }
+  for (int i = 0; i < 4; ++i) ws[i]->ensure(want[i]);
+  for (long long r0 = 0; r0 < Nnew; r0 += rows) {
+    const long long n = std::min(rows, Nnew - r0), sK = n * M;
+    HIP_TRY(hipMemcpyAsync(pX.p, Xnew + r0 * P, sizeof(double) * n * P, hipMemcpyHostToDevice, st));
+    PathsArgs fa;
+    fa.P = P, fa.Q = Q, fa.Lf = Lf, fa.ldx = P, fa.rows = n, fa.sX = 0;
+    fa.X = pX.d(), fa.omega = ps.omega.d(), fa.cq = ps.cq.d(), fa.Phi = pPhi.d();
+    launch_paths_features(fa, st);
+    RbfBatch rbt;
+    rbt.nq = Q, rbt.var = ps.var.d(), rbt.ell = ps.ell.d(), rbt.sZ = P, rbt.sK = sK;
+    launch_rbf(pX.d(), P, n, P, ps.Z.d(), Q * P, M, 0.0, 1.0, pA.d(), false, st, nullptr, true, &rbt);   // A_q: K_uf as the strict qf_chunk rounds it
+    HIP_TRY(hipMemsetAsync(pF.p, 0, sizeof(double) * nc * n, st));
+    for (int q = 0; q < Q; ++q) {     // F[(s, j)][i] += sum_k Theta~_q[k][(s, j)] Phi_q[i][k] + sum_m V~_q[m][(s, j)] A_q[i][m]
+      GemmArgs g;
+      g.A = ps.Theta.d() + (long long)q * K2 * nc, g.lda = (int)nc, g.a_kmajor = 1;
+      g.B = pPhi.d() + (long long)q * n * K2, g.ldb = (int)K2, g.b_kmajor = 0;
+      g.C = pF.d(), g.ldc = (int)n;
+      g.M = (int)nc, g.N = (int)n, g.K = (int)K2;
+      g.alpha = 1.0, g.beta = 1.0;
+      launch_gemm_f64(g, st);
+      g.A = ps.V.d() + (long long)q * M * nc;
+      g.B = pA.d() + (long long)q * sK, g.ldb = M;
+      g.K = M;
+      launch_gemm_f64(g, st);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy2DAsync(F + r0, sizeof(double) * Nnew, pF.p, sizeof(double) * n, sizeof(double) * n, (size_t)nc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (pX is reused by the next chunk's upload)
+  }
+}
+
+void hmogp_engine::paths_state(int id, double* omega, double* theta, double* v, double* u) {
+  if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to draw paths from"};
+  PathSet& ps = path_set(id);
+  HIP_TRY(hipSetDevice(device));
+  const long long K2 = 2LL * ps.Lf, nc = (long long)ps.nD * ps.S;
+  if (omega) HIP_TRY(hipMemcpyAsync(omega, ps.omega.p, sizeof(double) * Q * ps.Lf * P, hipMemcpyDeviceToHost, st));
+  if (theta) HIP_TRY(hipMemcpyAsync(theta, ps.Theta.p, sizeof(double) * Q * K2 * nc, hipMemcpyDeviceToHost, st));
+  if (v) HIP_TRY(hipMemcpyAsync(v, ps.V.p, sizeof(double) * Q * M * nc, hipMemcpyDeviceToHost, st));
+  if (u) HIP_TRY(hipMemcpyAsync(u, ps.u.p, sizeof(double) * Q * ps.S * M, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+}
+
+void hmogp_engine::paths_free(int id) {
+  if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to draw paths from"};
+  PathSet& ps = path_set(id);
+  HIP_TRY(hipSetDevice(device));
+  ps.reset();
+  bool any = false;
+  for (const PathSet& o : path_sets) any = any || o.live;
+  if (!any)
+    for (DevBuf* b : {&paths_wX, &paths_wPhi, &paths_wA, &paths_wF}) b->release();
+}

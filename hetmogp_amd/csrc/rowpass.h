@@ -173,6 +173,25 @@ void launch_joint_normal(unsigned long long seed, int S, long long n, double* Z,
 // mean[j * N + i] = m[i * Df + d[j]]: the joint vector's function-major mean out of q(f)'s [N][Df] rows (i0: first row of the chunk)
 void launch_joint_gather(const double* m, int Df, const int* d, int nD, long long N, long long i0, long long nrows, double* mean,
                          hipStream_t s);
+// Pathwise posterior samples (paths.hip).  The feature map of `rows` inputs for every latent:
+//   Phi[q][i][l] = c_q cos(pi t), Phi[q][i][Lf + l] = c_q sin(pi t), t = sum_p omega[q][l][p] x_ip in p order (one sincospi per (i, l)).
+// X: row i of latent q at X + q sX + i ldx (sX = 0: the same rows for every latent; the inducing inputs: X = Z, ldx = Q P, sX = P);
+// omega: [Q][Lf][P]; cq: [Q]; Phi: [Q][rows][2 Lf].  Every pointer is device memory.  A value depends on its own row and frequency alone.
+struct PathsArgs {
+  int P = 1, Q = 1, Lf = 1, ldx = 1;
+  long long rows = 0, sX = 0;
+  const double *X = nullptr, *omega = nullptr, *cq = nullptr;
+  double* Phi = nullptr;
+};
+void launch_paths_features(const PathsArgs& a, hipStream_t s);
+// The draws of one path set (header of include/hetmogp_hip.h's paths block: the stream tags): omega [Q][Lf][P] = zeta / (pi ell_q);
+// theta [Q][S][2 Lf]; eps [Q][S][M]; u [Q][S][M] = m_q (mu: [M][Q]) for the b_tri product u += eps L_q^T to accumulate onto
+void launch_paths_draw(unsigned long long seed, int Q, int P, int Lf, int S, int M, const double* ell, const double* mu, double* omega,
+                       double* theta, double* eps, double* u, hipStream_t s);
+// Theta~[q][k][s nD + j] = w[q][j] theta[q][s][k] + sk[q][j] theta'(d[j], q, s)[k];  V~[q][m][s nD + j] = w[q][j] v[q][s][m]
+// (w, sk: [Q][nD] -- W_q[d_j], sqrt(kappa_q[d_j]); d: [nD]; theta: [Q][S][2 Lf]; v: [Q][S][M])
+void launch_paths_scale(unsigned long long seed, int Q, int Lf, int S, int M, int nD, const int* d, const double* w, const double* sk,
+                        const double* theta, const double* v, double* Theta, double* V, hipStream_t s);
 // Gradients of q(f) with respect to the new inputs (xgrad.hip): gp[q][i][j] = (1 / l_q^2) sum_m a_qm A_q[i][m] (z_qmj - x_ij),
 // gc[q][i][j] = (2 / l_q^2) sum_m T_q[i][m] A_q[i][m] (z_qmj - x_ij) for the n rows of one chunk.  A, T: [Q][sK], n x M row-major (lda = M);
 // Z: latent q's inducing inputs at Z + q P, row stride ldz; a: [Q][M]; ell: [Q]; X: [n][P]; gp, gc: [Q][ldo][P].  Every pointer is device

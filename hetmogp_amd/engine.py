@@ -164,11 +164,13 @@ class Engine(object):
         self._pcache = None
         self._ocache = {}
         self._pinned_out = None
+        self._paths_shape = {}           # live path sets: slot id -> (size, nD, num_features)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             lib.hmogp_destroy(self._h)
             self._h = None
+            self._paths_shape = {}      # (the engine's path sets went with it)
 
     def __del__(self):
         try:
@@ -411,6 +413,44 @@ class Engine(object):
         if return_factor:
             return F, dict(mean=mean, L=L, jitter=float(jit.value), rung=int(rung.value))
         return F
+
+    # pathwise (Matheron) posterior samples: a path set is drawn once and evaluated anywhere, any number of times
+    def paths_create(self, functions=None, size=1, num_features=1024, seed=0):
+        """Draw a path set -- `size` sample paths of the functions `functions` (None: all Df) with `num_features` random Fourier
+        frequencies per latent -- from the parameters of the last evaluation; returns its id.  At most _lib.PATHS_MAXSETS live sets."""
+        d = self._joint_functions(functions)
+        sid = C.c_int32(-1)
+        check(lib.hmogp_paths_create(self._h, d.shape[0], d.ctypes.data_as(_lib.c_int32_p), int(size), int(num_features),
+                                     int(seed) & (2 ** 64 - 1), C.byref(sid)), self._h)
+        self._paths_shape[int(sid.value)] = (int(size), d.shape[0], int(num_features))
+        return int(sid.value)
+
+    def _paths_dims(self, sid):
+        dims = self._paths_shape.get(int(sid))
+        if dims is None:       # (the library refuses the id with its own message)
+            check(lib.hmogp_paths_eval(self._h, int(sid), None, 0, None), self._h)
+            raise _lib.InvalidArgument("paths: unknown or freed path-set id")
+        return dims
+
+    def paths_eval(self, sid, Xnew):
+        """The paths of set `sid` at Xnew: (size, nD, N), the layout of `sample_f_joint`; the same function on every call, any N."""
+        Xnew = _f64(Xnew).reshape(-1, self.P)
+        S, nD, _ = self._paths_dims(sid)
+        F = np.zeros((S, nD, Xnew.shape[0]))
+        check(lib.hmogp_paths_eval(self._h, int(sid), _p(Xnew), Xnew.shape[0], _p(F)), self._h)
+        return F
+
+    def paths_state(self, sid):
+        """The set's state: dict(omega (Q, Lf, P), theta (Q, 2 Lf, S, nD) = W theta + sqrt(kappa) theta', v (Q, M, S, nD) = W v, u (Q, S, M))."""
+        S, nD, Lf = self._paths_dims(sid)
+        out = dict(omega=np.zeros((self.Q, Lf, self.P)), theta=np.zeros((self.Q, 2 * Lf, S, nD)), v=np.zeros((self.Q, self.M, S, nD)),
+                   u=np.zeros((self.Q, S, self.M)))
+        check(lib.hmogp_paths_state(self._h, int(sid), _p(out["omega"]), _p(out["theta"]), _p(out["v"]), _p(out["u"])), self._h)
+        return out
+
+    def paths_free(self, sid):
+        check(lib.hmogp_paths_free(self._h, int(sid)), self._h)
+        self._paths_shape.pop(int(sid), None)
 
     def predict_f_grad(self, Xnew, return_mv=False):
         """Gradients of q(f) with respect to the inputs Xnew: (dm (N, Df, P), dv (N, Df, P)), dm[i, d, j] = d m_d / d x_j and

@@ -876,24 +876,41 @@ class SVMOGP(object):
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         return int(seed)
 
-    def posterior_samples_f(self, Xnew, size=10, functions=None, seed=None):
+    def sample_paths(self, size=10, functions=None, num_features=1024, seed=None):
+        """`size` posterior sample paths of the functions `functions` (None: all) as FUNCTIONS (pathwise conditioning): a
+        `PosteriorPaths` that can be evaluated at any inputs, any number of times -- the same draw on every call, no bound on N.  The
+        prior part is `num_features` random Fourier frequencies per latent; the update through the inducing variables is exact.  A
+        snapshot of the model as it is now.  seed=None draws the seed from NumPy's global generator."""
+        self._refresh()
+        return PosteriorPaths(self, size, functions, num_features, self._joint_seed(seed))
+
+    def posterior_samples_f(self, Xnew, size=10, functions=None, seed=None, method="joint", num_features=1024):
         """`size` sample paths of the functions `functions` (None: all) at Xnew, drawn JOINTLY over functions and inputs from the
         posterior of `predict_f(full_cov=True)` (GPy's `posterior_samples_f`): (size, N, nD).  Draw s depends on (seed, s)
-        only, not on `size`; seed=None draws the seed from NumPy's global generator."""
+        only, not on `size`; seed=None draws the seed from NumPy's global generator.  method="pathwise" (DESIGN 9v): a temporary
+        `sample_paths` set of `num_features` frequencies evaluated at Xnew -- no bound on nD * N."""
+        if method == "pathwise":
+            with self.sample_paths(size=size, functions=functions, num_features=num_features, seed=seed) as paths:
+                return paths(Xnew)
+        if method != "joint":
+            raise ValueError("method must be 'joint' or 'pathwise'")
         self._refresh()
         F = self._engine.sample_f_joint(np.asarray(Xnew, dtype=float).reshape(-1, self.Xdim), functions, size=size,
                                         seed=self._joint_seed(seed))
         return np.ascontiguousarray(np.transpose(F, (0, 2, 1)))
 
-    def posterior_samples(self, Xnew, task, size=10, seed=None):
+    def posterior_samples(self, Xnew, task, size=10, seed=None, method="joint", num_features=1024):
         """`size` draws of task `task`'s output at Xnew (GPy's `posterior_samples`): the task's functions are drawn jointly
-        (`posterior_samples_f`), each draw is then pushed through the likelihood's sampler on the device (`hmogp_sample`, keyed by
-        seed + 1 and the row s N + i).  (size, N); (size, N, K) for Dirichlet."""
+        (`posterior_samples_f`, by `method`), each draw is then pushed through the likelihood's sampler on the device (`hmogp_sample`,
+        keyed by seed + 1 and the row s N + i).  (size, N); (size, N, K) for Dirichlet."""
         t = int(task)
         lik = self.likelihood.likelihoods_list[t]
         cols = [d for d in range(self.num_output_funcs) if self.Y_metadata["function_index"].flatten()[d] == t]
         seed = self._joint_seed(seed)
-        F = self.posterior_samples_f(Xnew, size=size, functions=cols, seed=seed)
+        if method == "joint":
+            F = self.posterior_samples_f(Xnew, size=size, functions=cols, seed=seed)
+        else:
+            F = self.posterior_samples_f(Xnew, size=size, functions=cols, seed=seed, method=method, num_features=num_features)
         S, N, J = F.shape
         Y = np.asarray(lik.samples(F.reshape(S * N, J), seed=seed + 1))        # one launch: row s N + i is draw s at input i
         return Y.reshape(S, N, -1) if lik.name == "Dirichlet" else Y.reshape(S, N)
@@ -1090,3 +1107,48 @@ class SVMOGP(object):
 
 
 HetMOGP = SVMOGP  # the README's name for the class (README.md:35); the reference's code only defines SVMOGP
+
+
+class PosteriorPaths(object):
+    """`size` posterior sample paths of a model's functions as functions (`SVMOGP.sample_paths`; pathwise conditioning).
+    `paths(Xnew)` -> (size, N, nD), the orientation of `posterior_samples_f`: the same draw on every call, at any inputs.  A snapshot
+    of the model at the time of the draw.  A context manager; `close()` frees the set on the device, any use after it raises."""
+
+    def __init__(self, model, size, functions, num_features, seed):
+        self._engine = model._engine
+        self._xdim = model.Xdim
+        self.functions = list(range(model.num_output_funcs)) if functions is None else [int(f) for f in np.ravel(functions)]
+        self.size, self.num_features, self.seed = int(size), int(num_features), int(seed)
+        self._id = None
+        self._id = self._engine.paths_create(functions, size=self.size, num_features=self.num_features, seed=self.seed)
+
+    def _live(self):
+        if self._id is None:
+            raise ValueError("PosteriorPaths: the path set is closed")
+        return self._id
+
+    def __call__(self, Xnew):
+        F = self._engine.paths_eval(self._live(), np.asarray(Xnew, dtype=float).reshape(-1, self._xdim))
+        return np.ascontiguousarray(np.transpose(F, (0, 2, 1)))
+
+    def state(self):
+        """dict(omega (Q, Lf, P), theta (Q, 2 Lf, size, nD), v (Q, M, size, nD), u (Q, size, M)): the set's frequencies and weights."""
+        return self._engine.paths_state(self._live())
+
+    def close(self):
+        sid, self._id = self._id, None
+        if sid is not None and getattr(self._engine, "_h", None):
+            self._engine.paths_free(sid)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -631,6 +631,44 @@ int hmogp_qf_input_grad(int32_t device, int64_t N, int32_t P, const double* X /*
 int hmogp_predict_f_grad(hmogp_handle h, const double* Xnew, int64_t Nnew, double* m /* [Nnew, Df] or NULL */,
                          double* v /* [Nnew, Df] or NULL */, double* dm /* [Nnew, Df, P] */, double* dv /* [Nnew, Df, P] */);
 
+/* Posterior sample paths as FUNCTIONS: pathwise (Matheron) conditioning (Wilson, Borovitskiy, Terenin, Mostowsky & Deisenroth,
+ * ICML 2020).  A path set = (nD distinct functions d_index[j], S samples, Lf random Fourier frequencies per latent, a 64-bit seed) is drawn
+ * ONCE from the parameters of the last evaluation -- q(u_q) = N(m_q, L_q L_q^T), K_q = k_q(Z_q, Z_q) -- and can then be
+ * evaluated at any inputs, any number of times: the same function on every call, O(N (Lf + M)) per sample, no bound on N.
+ *   draws (z0 of the counter-based normal generator at (seed, n, s, pair); the pair is the stream tag):
+ *     zeta_{q,l,p}    n = l,             s = 4 q + p,   pair 1      frequencies, shared by all samples: omega_{q,l,p} = zeta / (pi l_q)
+ *     theta_{q,s}[k]  n = k < 2 Lf,      s = s Q + q,   pair 2      prior weights
+ *     eps_{q,s}[m]    n = m < M,         s = s Q + q,   pair 3      q(u) normals
+ *     theta'_{d,q,s}  n = d 2 Lf + k,    s = s Q + q,   pair 4      weights of the kappa part of FUNCTION d (its index, not its position)
+ *   features: t_l(x) = sum_p omega_{q,l,p} x_p (in p order), c_q = sqrt(variance_q / Lf), phi_{q,l} = c_q cos(pi t_l), phi_{q,Lf+l} = c_q sin(pi t_l)
+ *   (sincospi: exact argument reduction); E[phi_q(x)^T phi_q(x')] = k_q(x, x').  The STORED omega is the contract.
+ *   paths:  u_{q,s} = m_q + L_q eps_{q,s},   v_{q,s} = K_q^-1 (u_{q,s} - Phi_q(Z_q) theta_{q,s})   (row solves against the set's own factor, below),
+ *     f_d^s(x) = sum_q [ phi_q(x)^T (W_q[d] theta_{q,s} + sqrt(kappa_q[d]) theta'_{d,q,s}) + W_q[d] k_q(x, Z_q)^T v_{q,s} ]
+ * Given the frequencies the S paths are i.i.d. Gaussian with hmogp_predict_f's mean exactly and hmogp_predict_f_joint's covariance with k_q
+ * replaced by phi_q^T phi_q; at the inducing inputs the update cancels the feature error identically.  A function's paths depend neither on
+ * S nor on which other functions were asked for; a row's value does not depend on Nnew or on the chunks; the set has one set of bits
+ * whatever mode the evaluation ran in.  For that the set does NOT read the factor the evaluation left behind (the small-model kernel's
+ * and the blocked factorisation's differ in their last bits): it forms K_q from its own copy of Z in GPy's rounding order and factorises
+ * it with the blocked kernels of hmogp_jitchol_inv on the jitter rung the evaluation took -- compare v against that, not against a Luu
+ * obtained elsewhere.  A set is a SNAPSHOT (its own copies of Z, omega, c_q, the weights, l_q, variance_q): later
+ * evaluations, q(u) updates and hmogp_set_lik_params do not change it; hmogp_destroy frees every live set.
+ * hmogp_paths_create: *id = the slot of the new set.  hmogp_paths_eval: F [S, nD, Nnew], the layout of hmogp_sample_f_joint.
+ * hmogp_paths_state (each pointer may be NULL): omega [Q, Lf, P]; theta [Q, 2 Lf, S, nD] = W theta + sqrt(kappa) theta'; v [Q, M, S, nD] = W v;
+ * u [Q, S, M].  hmogp_paths_free releases the slot.
+ * HMOGP_E_INVALID for a NULL handle; then HMOGP_E_STATE before the first evaluation; HMOGP_E_INVALID for nD < 1, an index out of range or
+ * repeated, S < 1, Lf < 1, Lf > HMOGP_PATHS_MAXFEAT, nD S > HMOGP_PATHS_MAXCOLS, no free slot (HMOGP_PATHS_MAXSETS live sets), a NULL id, an
+ * unknown or freed id, Nnew < 0, Xnew or F NULL with Nnew > 0 -- every refusal before any device call; then HMOGP_E_INVALID, with the bytes
+ * needed in the message, if the set's state and the draw's workspace exceed the device's free memory (asked before anything is
+ * allocated).  Nnew = 0 returns success at once.  New symbols only: ABI version 8 stays.                                             */
+#define HMOGP_PATHS_MAXFEAT 8192     /* Lf */
+#define HMOGP_PATHS_MAXCOLS 4096     /* nD * S */
+#define HMOGP_PATHS_MAXSETS 16       /* live path sets per engine */
+int hmogp_paths_create(hmogp_handle h, int32_t nD, const int32_t* d_index /* [nD] */, int32_t S, int32_t Lf, uint64_t seed, int32_t* id);
+int hmogp_paths_eval(hmogp_handle h, int32_t id, const double* Xnew /* [Nnew, P] */, int64_t Nnew, double* F /* [S, nD, Nnew] */);
+int hmogp_paths_state(hmogp_handle h, int32_t id, double* omega /* [Q, Lf, P] */, double* theta /* [Q, 2Lf, S, nD] */,
+                      double* v /* [Q, M, S, nD] */, double* u /* [Q, S, M] */);   /* each may be NULL */
+int hmogp_paths_free(hmogp_handle h, int32_t id);
+
 /* Data generation on the device: one draw Y[n] ~ p(y | F[n, :]) per row with the link functions and clips of the
  * reference's `<likelihood>.samples` (het_likelihood.py:72-83 -> e.g. gamma.py:43-50, categorical.py:65-75; labels of
  * Categorical are 1..K).  Counter-based generator keyed by (seed, row): reproducible, but a different stream than

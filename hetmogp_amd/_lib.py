@@ -164,6 +164,7 @@ EXPORTS = {
     "hmogp_predict_f_grad": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hmogp_paths_create": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_uint64, c_int32_p]),
     "hmogp_paths_eval": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_double_p]),
+    "hmogp_paths_eval_grad": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p]),
     "hmogp_paths_state": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hmogp_paths_free": (C.c_int, [C.c_void_p, C.c_int32]),
     "hmogp_sample": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint64, c_double_p, c_double_p]),

@@ -354,6 +354,10 @@ int hmogp_paths_eval(hmogp_handle h, int32_t id, const double* Xnew, int64_t Nne
   if (!h) return paths_no_handle("hmogp_paths_eval");
   return guarded(h, [&] { h->paths_eval(id, Xnew, Nnew, F); });
 }
+int hmogp_paths_eval_grad(hmogp_handle h, int32_t id, const double* Xnew, int64_t Nnew, double* F, double* G) {
+  if (!h) return paths_no_handle("hmogp_paths_eval_grad");
+  return guarded(h, [&] { h->paths_eval_grad(id, Xnew, Nnew, F, G); });
+}
 int hmogp_paths_state(hmogp_handle h, int32_t id, double* omega, double* theta, double* v, double* u) {
   if (!h) return paths_no_handle("hmogp_paths_state");
   return guarded(h, [&] { h->paths_state(id, omega, theta, v, u); });

@@ -575,19 +575,23 @@ struct hmogp_engine {
     int nD = 0, S = 0, Lf = 0;
     unsigned long long seed = 0;
     DevBuf Z, omega, cq, var, ell, Theta, V, u;   // Z [M][Q P] | [Q][Lf][P] | [Q] | [Q] | [Q] | [Q][2 Lf][S nD] | [Q][M][S nD] | [Q][S][M]
+    DevBuf dTheta;                                // [Q][P][2 Lf][S nD], built at the set's first gradient call (empty until then)
     void reset() {
-      for (DevBuf* b : {&Z, &omega, &cq, &var, &ell, &Theta, &V, &u}) b->release();
+      for (DevBuf* b : {&Z, &omega, &cq, &var, &ell, &Theta, &V, &u, &dTheta}) b->release();
       live = false;
     }
   };
   PathSet path_sets[HMOGP_PATHS_MAXSETS];
   DevBuf paths_wX, paths_wPhi, paths_wA, paths_wF;   // chunk workspace of paths_eval (X, Phi, A_q, F): grows as needed, released with the last live set
+  DevBuf paths_wD, paths_wG, paths_wGt;              // ... and of paths_eval_grad: D(p) [P][Q][rows][M], G [P][S nD][rows], its transpose
   // rows per chunk of an evaluation: the feature workspace Phi [Q][rows][2 Lf] of one chunk stays within this many bytes (1 GiB; so do
   // A_q and the chunk of F, each).  The products are one 128-row tile of S nD columns wide: the chunk's rows are what fills the device
   static constexpr long long PATHS_PHI_BUDGET = 1LL << 30;
   PathSet& path_set(int id);    // HMOGP_E_INVALID for an unknown or freed id
   void paths_create(int nD, const int* d, int S, int Lf, unsigned long long seed, int* id);
   void paths_eval(int id, const double* Xnew, long long Nnew, double* F);
+  // G [S][nD][Nnew][P] = d f_d^s / d x_p at Xnew; F (may be null) is paths_eval's, bit for bit
+  void paths_eval_grad(int id, const double* Xnew, long long Nnew, double* F, double* G);
   void paths_state(int id, double* omega, double* theta, double* v, double* u);
   void paths_free(int id);
 

@@ -705,6 +705,110 @@ void hmogp_engine::paths_eval(int id, const double* Xnew, long long Nnew, double
   }
 }
 
+// G[s][j][i][p] = d f_{d_j}^s / d x_p at Xnew.  Both parts of a path are linear in what the set stores: the prior part is the
+// evaluation's own feature image Phi against the rotated operand Theta~(p) (built at the set's first gradient call, kept with it), the
+// update part the P derivative images D(p)_q = A_q .* (z_qp - x_p) / l_q^2 of the evaluation's own A_q against V~.  The products are
+// paths_eval's, issued per p into G [P][S nD][rows]: every launch has a shape paths_eval runs, an entry's k-order depends on none of N,
+// the chunks, S, the function list, or whether F was asked for.  F (optional) comes from the same Phi and A_q by paths_eval's two
+// products per latent: its bits.  The workspace is transposed to the caller's layout (P innermost) on the device, then one pitched
+// download per chunk.  Every refusal comes before the first device call, the memory question before the allocations it is about.
+void hmogp_engine::paths_eval_grad(int id, const double* Xnew, long long Nnew, double* F, double* G) {
+  if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to draw paths from"};
+  PathSet& ps = path_set(id);
+  if (Nnew < 0) throw EngineError{HMOGP_E_INVALID, "paths: Nnew must be >= 0"};
+  if (Nnew > 0 && (!Xnew || !G)) throw EngineError{HMOGP_E_INVALID, "paths: Xnew and G must be given"};
+  if (Nnew == 0) return;
+
+  HIP_TRY(hipSetDevice(device));
+  const int Lf = ps.Lf;
+  const long long K2 = 2LL * Lf, nc = (long long)ps.nD * ps.S;
+  // rows per chunk: paths_eval's rule with the derivative images D [P][Q][rows][M] and the gradient workspace G [P][S nD][rows] counted
+  // against the same budget (a multiple of 128 rows, at least 128), at most the engine's chunk_rows
+  const long long widest = std::max<long long>(std::max<long long>(Q * K2, (long long)P * Q * M), P * nc);
+  long long rows = std::max<long long>(128, PATHS_PHI_BUDGET / (8 * widest) / 128 * 128);
+  rows = std::min(std::min(rows, chunk), std::min<long long>(Nnew, 1LL << 20));
+  DevBuf &pX = paths_wX, &pPhi = paths_wPhi, &pA = paths_wA, &pF = paths_wF, &pD = paths_wD, &pG = paths_wG, &pGt = paths_wGt;
+  const size_t dth_bytes = sizeof(double) * Q * P * K2 * nc;
+  const size_t want[7] = {sizeof(double) * rows * P,     sizeof(double) * Q * rows * K2,  sizeof(double) * Q * rows * M,
+                          F ? sizeof(double) * nc * rows : 0, sizeof(double) * P * Q * rows * M, sizeof(double) * P * nc * rows,
+                          P > 1 ? sizeof(double) * P * nc * rows : 0};
+  DevBuf* const ws[7] = {&pX, &pPhi, &pA, &pF, &pD, &pG, &pGt};
+  {   // the memory question: the set's rotated operand (first gradient call only) and the workspace's growth, before any allocation
+    const double rot = ps.dTheta.p ? 0.0 : (double)dth_bytes;
+    double grow = 0.0;
+    for (int i = 0; i < 7; ++i)
+      if (want[i] > ws[i]->bytes) grow += (double)want[i] - (double)ws[i]->bytes;
+    if (rot + grow > 0.0) {
+      size_t free_b = 0, total_b = 0;
+      HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+      if (rot + grow > (double)free_b) {
+        char buf[256];
+        std::snprintf(buf, sizeof buf, "paths: the gradient's rotated operand (%.0f bytes) and the chunk workspace's growth (%.0f bytes) need %.0f bytes, the device has %.0f free",
+                      rot, grow, rot + grow, (double)free_b);
+        throw EngineError{HMOGP_E_INVALID, buf};
+      }
+    }
+  }
+  if (!ps.dTheta.p) {
+    ps.dTheta.ensure(dth_bytes);
+    launch_paths_dtheta(Q, P, Lf, (int)nc, ps.omega.d(), ps.Theta.d(), ps.dTheta.d(), st);
+    HIP_TRY(hipGetLastError());
+  }
+  for (int i = 0; i < 7; ++i) ws[i]->ensure(want[i]);
+  for (long long r0 = 0; r0 < Nnew; r0 += rows) {
+    const long long n = std::min(rows, Nnew - r0), sK = n * M;
+    HIP_TRY(hipMemcpyAsync(pX.p, Xnew + r0 * P, sizeof(double) * n * P, hipMemcpyHostToDevice, st));
+    PathsArgs fa;
+    fa.P = P, fa.Q = Q, fa.Lf = Lf, fa.ldx = P, fa.rows = n, fa.sX = 0;
+    fa.X = pX.d(), fa.omega = ps.omega.d(), fa.cq = ps.cq.d(), fa.Phi = pPhi.d();
+    launch_paths_features(fa, st);
+    RbfBatch rbt;
+    rbt.nq = Q, rbt.var = ps.var.d(), rbt.ell = ps.ell.d(), rbt.sZ = P, rbt.sK = sK;
+    launch_rbf(pX.d(), P, n, P, ps.Z.d(), Q * P, M, 0.0, 1.0, pA.d(), false, st, nullptr, true, &rbt);   // A_q: as paths_eval forms it
+    RbfDxArgs dx;
+    dx.P = P, dx.Q = Q, dx.M = M, dx.ldz = Q * P, dx.n = n, dx.sK = sK;
+    dx.A = pA.d(), dx.X = pX.d(), dx.Z = ps.Z.d(), dx.ell = ps.ell.d(), dx.D = pD.d();
+    launch_rbf_dx(dx, st);
+    GemmArgs g;
+    g.lda = (int)nc, g.a_kmajor = 1, g.b_kmajor = 0;
+    g.ldc = (int)n, g.M = (int)nc, g.N = (int)n;
+    g.alpha = 1.0, g.beta = 1.0;
+    if (F) {
+      HIP_TRY(hipMemsetAsync(pF.p, 0, sizeof(double) * nc * n, st));
+      for (int q = 0; q < Q; ++q) {   // paths_eval's two products per latent, from the same Phi and A_q
+        g.C = pF.d();
+        g.A = ps.Theta.d() + (long long)q * K2 * nc;
+        g.B = pPhi.d() + (long long)q * n * K2, g.ldb = (int)K2, g.K = (int)K2;
+        launch_gemm_f64(g, st);
+        g.A = ps.V.d() + (long long)q * M * nc;
+        g.B = pA.d() + (long long)q * sK, g.ldb = M, g.K = M;
+        launch_gemm_f64(g, st);
+      }
+    }
+    HIP_TRY(hipMemsetAsync(pG.p, 0, sizeof(double) * P * nc * n, st));
+    for (int p = 0; p < P; ++p)
+      for (int q = 0; q < Q; ++q) {   // G[p][(s, j)][i] += sum_k Theta~(p)_q[k][(s, j)] Phi_q[i][k] + sum_m V~_q[m][(s, j)] D(p)_q[i][m]
+        g.C = pG.d() + (long long)p * nc * n;
+        g.A = ps.dTheta.d() + ((long long)q * P + p) * K2 * nc;
+        g.B = pPhi.d() + (long long)q * n * K2, g.ldb = (int)K2, g.K = (int)K2;
+        launch_gemm_f64(g, st);
+        g.A = ps.V.d() + (long long)q * M * nc;
+        g.B = pD.d() + ((long long)p * Q + q) * sK, g.ldb = M, g.K = M;
+        launch_gemm_f64(g, st);
+      }
+    const double* out = pG.d();
+    if (P > 1) {
+      launch_paths_gtrans(pG.d(), P, nc, n, pGt.d(), st);
+      out = pGt.d();
+    }
+    HIP_TRY(hipGetLastError());
+    if (F) HIP_TRY(hipMemcpy2DAsync(F + r0, sizeof(double) * Nnew, pF.p, sizeof(double) * n, sizeof(double) * n, (size_t)nc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpy2DAsync(G + r0 * P, sizeof(double) * Nnew * P, out, sizeof(double) * n * P, sizeof(double) * n * P, (size_t)nc,
+                             hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (pX is reused by the next chunk's upload)
+  }
+}
+
 void hmogp_engine::paths_state(int id, double* omega, double* theta, double* v, double* u) {
   if (!evaluated && !began) throw EngineError{HMOGP_E_STATE, "no evaluation to draw paths from"};
   PathSet& ps = path_set(id);
@@ -725,5 +829,5 @@ void hmogp_engine::paths_free(int id) {
   bool any = false;
   for (const PathSet& o : path_sets) any = any || o.live;
   if (!any)
-    for (DevBuf* b : {&paths_wX, &paths_wPhi, &paths_wA, &paths_wF}) b->release();
+    for (DevBuf* b : {&paths_wX, &paths_wPhi, &paths_wA, &paths_wF, &paths_wD, &paths_wG, &paths_wGt}) b->release();
 }

@@ -192,6 +192,22 @@ void launch_paths_draw(unsigned long long seed, int Q, int P, int Lf, int S, int
 // (w, sk: [Q][nD] -- W_q[d_j], sqrt(kappa_q[d_j]); d: [nD]; theta: [Q][S][2 Lf]; v: [Q][S][M])
 void launch_paths_scale(unsigned long long seed, int Q, int Lf, int S, int M, int nD, const int* d, const double* w, const double* sk,
                         const double* theta, const double* v, double* Theta, double* V, hipStream_t s);
+// Gradients of the paths with respect to the new inputs (pathsgrad.hip).  The rotated operand of the prior part,
+//   dTheta[q][p][l][c] = (pi omega[q][l][p]) Theta[q][Lf + l][c],  dTheta[q][p][Lf + l][c] = -(pi omega[q][l][p]) Theta[q][l][c]
+// (omega: [Q][Lf][P]; Theta: [Q][2 Lf][nc]; dTheta: [Q][P][2 Lf][nc]): d/dx_p (phi^T Theta) = phi^T dTheta(p).
+void launch_paths_dtheta(int Q, int P, int Lf, int nc, const double* omega, const double* Theta, double* dTheta, hipStream_t s);
+// The derivative images of A_q = k_q(X, Z_q) for the n rows of one chunk: D[p][q][i][m] = A[q][i][m] ((z_qmp - x_ip) inv_l2), inv_l2 =
+// 1 / (l_q l_q), in that order of operations.  A: [Q][sK], n x M row-major; D: [P][Q][sK]; Z: latent q's inducing inputs at Z + q P, row
+// stride ldz; X: [n][P]; ell: [Q].  Every pointer is device memory.  An entry depends on its own row, m and p alone.
+struct RbfDxArgs {
+  int P = 1, Q = 1, M = 0, ldz = 0;
+  long long n = 0, sK = 0;
+  const double *A = nullptr, *X = nullptr, *Z = nullptr, *ell = nullptr;
+  double* D = nullptr;
+};
+void launch_rbf_dx(const RbfDxArgs& g, hipStream_t s);
+// Gt[c][i][p] = G[p][c][i] (G: [P][nc][n], Gt: [nc][n][P]): the gradient workspace of a chunk into the caller's layout, P innermost
+void launch_paths_gtrans(const double* G, int P, long long nc, long long n, double* Gt, hipStream_t s);
 // Gradients of q(f) with respect to the new inputs (xgrad.hip): gp[q][i][j] = (1 / l_q^2) sum_m a_qm A_q[i][m] (z_qmj - x_ij),
 // gc[q][i][j] = (2 / l_q^2) sum_m T_q[i][m] A_q[i][m] (z_qmj - x_ij) for the n rows of one chunk.  A, T: [Q][sK], n x M row-major (lda = M);
 // Z: latent q's inducing inputs at Z + q P, row stride ldz; a: [Q][M]; ell: [Q]; X: [n][P]; gp, gc: [Q][ldo][P].  Every pointer is device

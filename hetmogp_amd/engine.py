@@ -440,6 +440,16 @@ class Engine(object):
         check(lib.hmogp_paths_eval(self._h, int(sid), _p(Xnew), Xnew.shape[0], _p(F)), self._h)
         return F
 
+    def paths_eval_grad(self, sid, Xnew, values=False):
+        """The gradients of the paths of set `sid` with respect to the inputs: G (size, nD, N, P), G[s, j, i, p] = d f / d x_p at
+        row i; with values=True (F, G), F the bits of `paths_eval`."""
+        Xnew = _f64(Xnew).reshape(-1, self.P)
+        S, nD, _ = self._paths_dims(sid)
+        G = np.zeros((S, nD, Xnew.shape[0], self.P))
+        F = np.zeros((S, nD, Xnew.shape[0])) if values else None
+        check(lib.hmogp_paths_eval_grad(self._h, int(sid), _p(Xnew), Xnew.shape[0], _p(F) if values else None, _p(G)), self._h)
+        return (F, G) if values else G
+
     def paths_state(self, sid):
         """The set's state: dict(omega (Q, Lf, P), theta (Q, 2 Lf, S, nD) = W theta + sqrt(kappa) theta', v (Q, M, S, nD) = W v, u (Q, S, M))."""
         S, nD, Lf = self._paths_dims(sid)

@@ -1131,6 +1131,17 @@ class PosteriorPaths(object):
         F = self._engine.paths_eval(self._live(), np.asarray(Xnew, dtype=float).reshape(-1, self._xdim))
         return np.ascontiguousarray(np.transpose(F, (0, 2, 1)))
 
+    def grad(self, Xnew):
+        """The gradients of the paths with respect to the inputs: (size, N, nD, P), [s, i, j, p] = d f_j^s / d x_p at row i -- the
+        exact derivative of the function `paths(Xnew)` evaluates, for gradient ascent on a sample path."""
+        G = self._engine.paths_eval_grad(self._live(), np.asarray(Xnew, dtype=float).reshape(-1, self._xdim))
+        return np.ascontiguousarray(np.transpose(G, (0, 2, 1, 3)))
+
+    def value_and_grad(self, Xnew):
+        """(`paths(Xnew)` (size, N, nD), `grad(Xnew)` (size, N, nD, P)) from one pass over Xnew; the values are the bits of `paths(Xnew)`."""
+        F, G = self._engine.paths_eval_grad(self._live(), np.asarray(Xnew, dtype=float).reshape(-1, self._xdim), values=True)
+        return np.ascontiguousarray(np.transpose(F, (0, 2, 1))), np.ascontiguousarray(np.transpose(G, (0, 2, 1, 3)))
+
     def state(self):
         """dict(omega (Q, Lf, P), theta (Q, 2 Lf, size, nD), v (Q, M, size, nD), u (Q, size, M)): the set's frequencies and weights."""
         return self._engine.paths_state(self._live())

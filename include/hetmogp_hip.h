@@ -668,6 +668,19 @@ int hmogp_paths_eval(hmogp_handle h, int32_t id, const double* Xnew /* [Nnew, P]
 int hmogp_paths_state(hmogp_handle h, int32_t id, double* omega /* [Q, Lf, P] */, double* theta /* [Q, 2Lf, S, nD] */,
                       double* v /* [Q, M, S, nD] */, double* u /* [Q, S, M] */);   /* each may be NULL */
 int hmogp_paths_free(hmogp_handle h, int32_t id);
+/* Gradients of the paths with respect to the new inputs: G [S, nD, Nnew, P], G[s, j, i, p] = d f_{d_j}^s / d x_p at row i of Xnew,
+ * the exact derivative of the function hmogp_paths_eval evaluates (both parts of a path are linear in the set's state):
+ *   d/dx_p phi_q(x)^T Theta~_q = phi_q(x)^T Theta~(p)_q,  Theta~(p)_q[l] = (pi omega_{q,l,p}) Theta~_q[Lf + l],  Theta~(p)_q[Lf + l] = -(pi omega_{q,l,p}) Theta~_q[l]
+ *   d/dx_p k_q(x, z_m) = k_q(x, z_m) ((z_{q,m,p} - x_p) (1 / (l_q l_q)))          ((z - x): one subtraction per term)
+ * summed over q from left to right.  F (optional): [S, nD, Nnew], the bits of hmogp_paths_eval.  Theta~(p) (P times the bytes of theta) is
+ * built at the set's first gradient call and kept with the set; a set that is never differentiated pays nothing.  A row's bits depend on
+ * neither Nnew nor the chunks nor S nor the other functions nor whether F is given, and are the same after a default-mode and a
+ * strict-mode evaluation.  Given the frequencies the mean of G over the samples is d m_d / d x of hmogp_predict_f_grad.
+ * HMOGP_E_INVALID for a NULL handle; HMOGP_E_STATE before the first evaluation; HMOGP_E_INVALID for an unknown or freed id, Nnew < 0, Xnew or G
+ * NULL with Nnew > 0 -- every refusal before any device call; then HMOGP_E_INVALID, with the bytes in the message, if Theta~(p) and the
+ * growth of the chunk workspace exceed the device's free memory.  Nnew = 0 returns success at once.  New symbol only: ABI version 8 stays. */
+int hmogp_paths_eval_grad(hmogp_handle h, int32_t id, const double* Xnew /* [Nnew, P] */, int64_t Nnew,
+                          double* F /* [S, nD, Nnew] or NULL */, double* G /* [S, nD, Nnew, P] */);
 
 /* Data generation on the device: one draw Y[n] ~ p(y | F[n, :]) per row with the link functions and clips of the
  * reference's `<likelihood>.samples` (het_likelihood.py:72-83 -> e.g. gamma.py:43-50, categorical.py:65-75; labels of

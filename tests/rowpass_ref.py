@@ -42,6 +42,9 @@ KERNEL_EXCEPTIONS = {}
 # them rounded up to a power of two), by the same rule and against R (measured 2026-10-19 on the CPU).  Two kinds move, both
 # sums of quadrature rows in NumPy's pairwise order: ve (24.7 on G) and sgv (24.2 on I).  Cases A-F stay on C_ORACLE.
 C_ORACLE_WIDE = dict(C_ORACLE, ve=32.0, sgv=32.0)
+# The `strict2` variants (the two-solve form of the strict q(f) mode) and case J need no constants of their own: the
+# float64 oracle's two-solve restatement stays within C_ORACLE on B, D, J and within C_ORACLE_WIDE on G, H in every kind (measured
+# 2026-10-21 on the CPU, table in DESIGN 9x; tests/test_rowpass_ref_cpu.py asserts it).  Nothing is widened.
 
 
 def c_kernel():
@@ -202,11 +205,16 @@ def row_side(prm, prob, side, X, Y):
     return rows
 
 
-def strict_rows(side, rows):
-    """X = K^ Luu^-T (forward substitution: Li is Luu^-1 by forward substitution) and its scale, added to every (task, latent)."""
+def strict_rows(side, rows, form=True):
+    """One-solve form: X = K^ Luu^-T (forward substitution: Li is Luu^-1 by forward substitution) and its scale, added to every (task,
+    latent).  form="two": A = K^ Kuu^-1 (both halves of the solve) and its scale s_A = |K^| |Kuu^-1|, from the cached K^ and Kuu^-1."""
     for o in rows:
         for q, lat in enumerate(o["lat"]):
-            if "Xs" not in lat:
+            if form == "two":
+                if "As" not in lat:
+                    lat["As"] = np.ascontiguousarray(lat["K"]) @ np.ascontiguousarray(side[q]["Kuui"].T).T
+                    lat["s_As"] = lat["K"].astype(np.float64) @ np.abs(side[q]["Kuui"]).astype(np.float64)
+            elif "Xs" not in lat:
                 lat["Xs"] = lat["K"] @ side[q]["Li"].T
                 lat["s_Xs"] = lat["K"].astype(np.float64) @ side[q]["Li_abs"].T
 
@@ -217,7 +225,10 @@ def reduce_rows(prm, prob, side, rows, X, batch_scale=None, row_begin=None, row_
     rows.  Returns (R, S): dicts kind -> array,
       ve (1,)  nneg (1,)  sgv (Df,)  H (Q, M, M)  r (Q, M)  dZ (Q, M, P)  sa (Q,)  sl (Q,)  swk (Q, Df)
       dKmn [q][d] (M, n_t)  dKdiag [q][d] (n_t,)  m [d] (n_t,)  v [d] (n_t,)
-    strict=True: H and r hold X^T diag(beta) X and X^T alpha (X = K^ Luu^-T), the rest is the same mathematics."""
+    strict=True: H and r hold X^T diag(beta) X and X^T alpha (X = K^ Luu^-T), the rest is the same mathematics.
+    strict="two": the two-solve form, H = A^T diag(beta) A and r = A^T alpha (A = K^ Kuu^-1, scale s_A = |K^| |Kuu^-1|): dVE_dS and
+    dVE_dmu themselves; the rest is the same mathematics."""
+    assert strict in (False, True, "two"), strict
     Q, M, P, T, Df = prob["Q"], prob["M"], prob["P"], prob["T"], prob["Df"]
     W = np.asarray(prm["W"], float)
     W0 = np.asarray(prm.get("W0", prm["W"]), float)
@@ -231,7 +242,8 @@ def reduce_rows(prm, prob, side, rows, X, batch_scale=None, row_begin=None, row_
              sa=np.zeros(Q), sl=np.zeros(Q), swk=np.zeros((Q, Df)), dKmn=[[None] * Df for _ in range(Q)],
              dKdiag=[[None] * Df for _ in range(Q)], m=[None] * Df, v=[None] * Df)
     if strict:
-        strict_rows(side, rows)
+        strict_rows(side, rows, strict)
+    gkey = "As" if strict == "two" else "Xs"
     for t in range(T):
         o, sl_ = rows[t], slice(b0[t], e0[t])
         ds = o["ds"]
@@ -256,7 +268,7 @@ def reduce_rows(prm, prob, side, rows, X, batch_scale=None, row_begin=None, row_
             s_alpha0, s_beta0 = sgm @ np.abs(w0), sgv @ np.abs(w0 * w)
             K, Pt = lat["K"][sl_], lat["Pt"][sl_]
             Kf, sP = K.astype(np.float64), lat["s_Pt"][sl_]
-            Kg, sKg = (lat["Xs"][sl_], lat["s_Xs"][sl_]) if strict else (K, Kf)
+            Kg, sKg = (lat[gkey][sl_], lat["s_" + gkey][sl_]) if strict else (K, Kf)
             if K.shape[0]:
                 R["H"][q] += np.ascontiguousarray((Kg * beta[:, None]).T) @ Kg
                 S["H"][q] += (sKg * s_beta[:, None]).T @ sKg

@@ -125,7 +125,7 @@ _REFS = {}
 
 def references():
     """{tag: {variant: dict(R, S, extra, bundle, strict[, B]), "case": (prm, prob, X, Y, rungs), "side", "facts"}}; variants: "default"
-    everywhere, "bs" and "strict" on D.  Built on first use.  The tail-only and small-model cases are whole jobs of their own in the
+    everywhere, "bs", "strict" and "strict2" (the two-solve form) on D.  Built on first use.  The tail-only and small-model cases are whole jobs of their own in the
     pool that forms the products of A-F by row ranges."""
     if _REFS:
         return _REFS
@@ -142,6 +142,7 @@ def references():
             if tag == "D":
                 v["bs"] = (dense_bundle(refs, tag, "bs"), False)
                 v["strict"] = (dense_bundle(refs, tag, "strict"), True)
+                v["strict2"] = (dense_bundle(refs, tag, "strict2"), "two")          # G = H and Kr = r: no M x M solve
             todo[tag] = dict(case=rc.dense_case(tag), side=refs[tag]["side"], variants=v)
         # the triangular inverses first, the largest first; the row-range jobs of a latent are issued as soon as its inverse is back
         Ls = [((tag, q), u["L"]) for tag, d in todo.items() for q, u in enumerate(d["side"])]

@@ -6,7 +6,7 @@ optimiser consumes -- `hmogp_engine::finish_enqueue` / `finish_tail` with the u-
   input   a float64 statistic bundle TAKEN AS EXACT (layout: `rr.layout` / `rr.split_bundle` / `rr.pack_bundle`; H_q is read from its
           lower triangle, as the engine reads it) and `rr.u_side(prm, prob, rungs)`; S^-1 = Linv^T Linv, Linv = `tri_inverse_ld(L)`.
   R       per latent, in np.longdouble:  G = K^-1 H K^-1, Kr = K^-1 r  (strict one-solve form: H = X^T beta X, r = X^T alpha in the
-          bundle, G = Luu^-T H Luu^-1, Kr = Luu^-T r);  dL_dS = G - (K^-1 - S^-1)/2;  g_L_u = 2 tril(dL_dS L), packed as
+          bundle, G = Luu^-T H Luu^-1, Kr = Luu^-T r;  strict two-solve form, strict="two": H = A^T beta A, r = A^T alpha, G = H, Kr = r);  dL_dS = G - (K^-1 - S^-1)/2;  g_L_u = 2 tril(dL_dS L), packed as
           `pack_gl_kernel` packs it;  g_m_u = Kr - a;  GSK = G S K^-1, KSK = K^-1 S K^-1;  dL_dKmm = sym(G - GSK - GSK^T - Kr a^T)
           - (K^-1 - KSK - a a^T)/2;  the K_zz-weighted row sums of `kzz_rows_kernel` (diagonal r^2 forced to 0, terms with r^2 = 0
           dropped);  the four KL terms, kl[q], elbo;  g_variance, g_lengthscale, g_W, g_kappa, g_Z assembled as `finish_tail` assembles
@@ -45,12 +45,21 @@ KL_BLOCKS = 64           # post.h: kl_terms_kernel's partials (element i of the 
 # two (measured 2026-10-19 on the CPU; the raw figures per case are in DESIGN 9g).
 C_ORACLE = dict(kl=1.0, elbo=1.0, g_m_u=128.0, g_L_u=128.0, dL_dS=128.0, g_variance=1.0, g_lengthscale=1.0, g_W=1.0, g_kappa=1.0,
                 g_Z=1.0, wv=32.0, winv=16.0)
+# The `strict2` variant of D (the two-solve form: G = H and Kr = r taken as exact), by the same rule and for that variant only:
+# per kind max(C_ORACLE, the float64 oracle's largest ratio on it rounded up to a power of two), measured 2026-10-21 on the CPU.  Two
+# kinds move, dL_dS (205.2) and g_L_u (191.2): with S(G) = |H| instead of |K^-1||H||K^-1| nothing hides the oracle's own error in
+# (K^-1 - S^-1) / 2 against 9f's inverse scale any more.  Every other kind stays within C_ORACLE.
+C_ORACLE_TWO = dict(C_ORACLE, g_L_u=256.0, dL_dS=256.0)
 # Elements beyond C_KERNEL that are inherent to the formulation: none.
 KERNEL_EXCEPTIONS = {}
 
 
 def c_kernel():
     return {k: max(16.0, 4.0 * c) for k, c in C_ORACLE.items()}
+
+
+def c_kernel_two():
+    return {k: max(16.0, 4.0 * c) for k, c in C_ORACLE_TWO.items()}
 
 
 def next_pow2(x):
@@ -92,8 +101,11 @@ def heavy_rows(job):
     Sinv = mm(Linv.T[r0:r1], Linv)
     out = dict(r0=r0, r1=r1, Sinv=Sinv, per=[])
     for H, strict in job["Hs"]:
-        left = Li.T[r0:r1] if strict else Ki[r0:r1]
-        G = mm(mm(left, H), Li if strict else Ki)
+        if strict == "two":          # the two-solve form: the bundle's H is dVE_dS itself, no M x M solve
+            G = np.array(H[r0:r1])
+        else:
+            left = Li.T[r0:r1] if strict else Ki[r0:r1]
+            G = mm(mm(left, H), Li if strict else Ki)
         dLdS = G - (Ki[r0:r1] - Sinv) / 2
         out["per"].append(dict(G=G, GSK=mm(mm(G, S), Ki), dLdS=dLdS, TL=mm(dLdS, L)))
     return out
@@ -134,7 +146,7 @@ def latent_values(prm, prob, q, u, b, hv, strict):
     products `hv` (dict G, GSK, dLdS, TL)."""
     M, P = prob["M"], prob["P"]
     Ki, a, m = u["Kuui"], u["a"], _ld(prm["m_u"][:, q])
-    Kr = (u["Li"].T if strict else Ki) @ b["r"]
+    Kr = b["r"] if strict == "two" else (u["Li"].T if strict else Ki) @ b["r"]
     G, GSK = hv["G"], hv["GSK"]
     KSK = u["C"] + Ki
     X = G - GSK - GSK.T - Kr[:, None] * a[None, :]
@@ -162,7 +174,9 @@ def latent_scales(prm, prob, q, u, Linv_abs, ab, strict, const=True):
     a_abs = KA @ np.abs(prm["m_u"][:, q])          # s_a of the u-side, completed by K^-1's own scale (const=False: s_a itself)
     s_a = a_abs if const else np.zeros(M)
     Ha = ab["H"]
-    if strict:
+    if strict == "two":          # G = H and Kr = r, taken as exact: their scales are their absolute values
+        S_G, S_Kr = Ha, ab["r"]
+    elif strict:
         S_G = LA.T @ Ha @ LA - s_Li.T @ Ha @ s_Li
         S_Kr = LA.T @ ab["r"]
     else:

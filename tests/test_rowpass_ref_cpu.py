@@ -26,9 +26,10 @@ def oracle_outputs(prm, prob, X, Y, rungs, bs=None, row_begin=None, row_end=None
     """Everything the criterion compares, from the float64 oracle: the bundle (`so.u_algebra` + `so.local_stats`), and from the
     per-row quantities behind it dL_dKmn = a gm^T + 2 w (gv P~)^T, dL_dKdiag = gv, and q(f)."""
     from oracle import svmogp_oracle as so
-    p = dict(prob, strict_qf=True) if strict else prob
+    p = dict(prob, strict_qf="two_solves" if strict == "two" else True) if strict else prob
     u = so.u_algebra(prm, p, rungs)
-    assert not strict or not u["strict_two"]           # the one-solve form, as the engine picks it at this conditioning
+    # strict=True: the one-solve form, as the engine picks it at this conditioning; strict="two": the two-solve form, forced
+    assert not strict or u["strict_two"] == (strict == "two")
     T, Q, Df = prob["T"], prob["Q"], prob["Df"]
     b = [0] * T if row_begin is None else row_begin
     e = [x.shape[0] for x in X] if row_end is None else row_end
@@ -103,6 +104,18 @@ def test_oracle_within_c_oracle(refs, tag):
         if name in rc.VARIANTS.get(tag, {}):
             kinds = rr.BUNDLE_KINDS if name == "strict" else rr.KINDS
             rr.check("oracle %s %s" % (tag, names[name]), variant_outputs(tag, name), *refs[tag][name], C, kinds)
+
+
+@pytest.mark.parametrize("tag", rc.STRICT2_TAGS)
+def test_oracle_two_solve_form_within_c_oracle(refs, tag):
+    """The float64 oracle's two-solve restatement (A = dpotrs, H = A^T diag(beta) A, r = A^T alpha in the bundle; q(f) through
+    p = A m and c = rowsum((A L)^2) - rowsum(A .* K^)) against the `strict2` reference, every element of the bundle kinds and of m, v:
+    B, D (also its row shard) and J within the present C_ORACLE, G and H within C_ORACLE_WIDE -- so the strict2 variants are held to
+    the present C_KERNEL / C_KERNEL_WIDE and nothing is widened (the measured table is in DESIGN 9x)."""
+    kinds = rr.BUNDLE_KINDS + ("m", "v")
+    for name in sorted(n for n in rc.VARIANTS[tag] if n.startswith("strict2")):
+        w = rr.check("oracle %s %s" % (tag, name), variant_outputs(tag, name), *refs[tag][name], c_oracle(tag), kinds)
+        print("[strict2] oracle %-2s %-13s %s" % (tag, name, " ".join("%s %.3g" % (k, w[k]) for k in kinds)))
 
 
 def test_constants_follow_the_rule():
@@ -205,6 +218,101 @@ def test_criterion_rejects_indexing_corruptions(refs):
         with pytest.raises(AssertionError):
             rr.check("corrupted: " + what, got, R, S, CK, (kind,))
     rr.check("uncorrupted D", clean, R, S, CK, rr.KINDS)
+
+
+def test_criterion_rejects_two_solve_corruptions(refs):
+    """Seeded corruptions of the ORACLE's own two-solve output of case D (arithmetic on arrays: nothing is run wrongly), each what an
+    indexing error in the two-solve code of the strict mode would leave behind.  Each must land beyond C_KERNEL by a factor 2^10 at
+    least; the ratios reached are recorded in DESIGN 9x."""
+    import scipy.linalg
+    from oracle import likelihoods_oracle as lo
+    prm, prob, X, Y, rungs = rc.dense_case("D")
+    R, S = refs["D"]["strict2"]
+    keep = {}
+    clean = oracle_outputs(prm, prob, X, Y, rungs, strict="two", keep=keep)
+    u, rows = keep["u"], keep["rows"]
+    CK, W, kap, Q, M = rr.c_kernel(), prm["W"], prm["kappa"], prob["Q"], prob["M"]
+    reached = []
+
+    def weights(o, q, gm=None, gv=None):
+        ds = [d for d in range(prob["Df"]) if prob["f_index"][d] == o["t"]]
+        gm, gv = (o["gm"] if gm is None else gm), (o["gv"] if gv is None else gv)
+        return gm @ W[q, ds], gv @ (W[q, ds] ** 2)
+
+    # 1. p_q = A_q m_u formed with the m_u of latent 1 - q: m directly, H through the row weights at the wrong m (v does not depend
+    #    on p: it cannot move and is asserted unchanged)
+    bad = dict(clean, m=[a.copy() for a in clean["m"]], H=np.zeros_like(clean["H"]))
+    for o in rows:
+        ds = [d for d in range(prob["Df"]) if prob["f_index"][d] == o["t"]]
+        mu = np.zeros_like(o["m"])
+        for j, d in enumerate(ds):
+            for q in range(Q):
+                mu[:, j] += W[q, d] * (o["Kg"][q] @ prm["m_u"][:, 1 - q])
+            bad["m"][d] = mu[:, j]
+        name, kw = prob["specs"][o["t"]]
+        _, gm, gv = lo.var_exp_all(name, Y[o["t"]], mu, o["v"], exact=False, **kw)
+        for q in range(Q):
+            _, beta = weights(o, q, gm, gv)
+            bad["H"][q] += (o["Kg"][q] * beta[:, None]).T @ o["Kg"][q]
+    reached += [("p_q from m_u of latent 1 - q", k, bad) for k in ("m", "H")]
+    assert rr.worst_ratios(bad, R, S, ("v",))["v"][0] == rr.worst_ratios(clean, R, S, ("v",))["v"][0]
+    # 2. columns 128 .. 255 of A without the backward update from columns 256 .. 383 (the backward half solves A Luu = X from the last
+    #    column block to the first: A_1 = (X_1 - A_2 Luu[2,1]) Luu[1,1]^-1): A_1 keeps A_2 Luu[2,1] Luu[1,1]^-1, A_0 is formed from that A_1
+    q = 1
+    Lu = u["Luu"][q]
+    b0, b1, b2 = slice(0, 128), slice(128, 256), slice(256, 384)
+    bad = dict(clean, H=clean["H"].copy(), r=clean["r"].copy())
+    bad["H"][q], bad["r"][q] = 0.0, 0.0
+    for o in rows:
+        A = o["Kg"][q].copy()
+        d1 = scipy.linalg.solve_triangular(Lu[b1, b1], (A[:, b2] @ Lu[b2, b1]).T, lower=True, trans="T").T
+        A[:, b1] += d1
+        A[:, b0] -= scipy.linalg.solve_triangular(Lu[b0, b0], (d1 @ Lu[b1, b0]).T, lower=True, trans="T").T
+        alpha, beta = weights(o, q)
+        bad["H"][q] += (A * beta[:, None]).T @ A
+        bad["r"][q] += A.T @ alpha
+    reached += [("A[:, 128:256] misses the update from 256:384", k, bad) for k in ("H", "r")]
+    # 3. rowsum(A .* K^) with K^ one row off inside one 16-row group (task 0, rows 256 .. 271)
+    o, k0 = rows[0], 256
+    A, K = o["Kg"][q][k0:k0 + 16], o["K"][q][k0:k0 + 16]
+    bad = dict(clean, v=[a.copy() for a in clean["v"]])
+    bad["v"][0][k0:k0 + 16] -= W[q, 0] ** 2 * (np.sum(A * np.roll(K, 1, axis=0), 1) - np.sum(A * K, 1))
+    reached.append(("rowsum(A .* K^): K^ one row off in a 16-row group", "v", bad))
+    for what, kind, got in reached:
+        ratio = rr.worst_ratios(got, R, S, (kind,))[kind][0]
+        print("[strict2] corruption %-46s %-3s ratio %.3g (C_KERNEL = %g, x 2^10 = %g)" % (what, kind, ratio, CK[kind], 1024 * CK[kind]))
+        assert ratio > 1024 * CK[kind], (what, kind, ratio)
+    rr.check("uncorrupted D strict2", clean, R, S, CK, rr.BUNDLE_KINDS + ("m", "v"))
+
+
+def test_case_K_takes_the_two_solve_form_by_itself(refs):
+    """Case K as committed: the condition estimate variance max diag(K_uu^-1) is >= 2e6 on latent 0 and <= 1e3 on latent 1, so
+    the strict mode picks the two-solve form with no switch set; float64 Cholesky of the unjittered K_uu succeeds; the neighbour at
+    1 h on the same data stays one-solve.  Closeness to R is conditioning-limited here: the float64 two-solve oracle's array-norm distances
+    from R are measured, printed and held against rc.K_ORACLE_DIST (and never 16 x below it: the record cannot go stale-loose)."""
+    from oracle import svmogp_oracle as so
+    prm, prob, X, Y, rungs = rc.auto_case()
+    u = so.u_algebra(prm, dict(prob, strict_qf=True), rungs)
+    est = [float(prm["variance"][q] * np.max(np.diag(u["Kuui"][q]))) for q in range(prob["Q"])]
+    cond = float(np.linalg.cond(u["Kuu"][0]))
+    print("[strict2] K estimate %s cond(K_uu) of latent 0 %.3g rungs %s (lengthscale / h = %g)" % (
+        " ".join("%.3g" % x for x in est), cond, u["rungs"], rc.K_CS))
+    assert est[0] >= 2e6 and est[1] <= 1e3 and u["strict_two"] and list(u["rungs"]) == rc.K_RUNGS
+    np.linalg.cholesky(u["Kuu"][0])
+    near = rc.auto_case(cs0=1.0)
+    assert not so.u_algebra(near[0], dict(prob, strict_qf=True), rungs)["strict_two"]
+    R, S = refs["K"]["two"]
+    assert float(R["nneg"][0]) == 0.0
+    got = oracle_outputs(prm, prob, X, Y, rungs, strict="two")
+    dist = rc.array_distances(got, R)
+    for k in rc.K_KINDS:
+        print("[strict2] K oracle %-4s max|oracle - R| / max|R| = %.3g (recorded %.2g)" % (k, dist[k], rc.K_ORACLE_DIST[k]))
+    # the two forms' H are different matrices: the reference of one cannot pass for the other
+    split = rc.array_distances(dict(H=np.asarray(R["H"], dtype=np.float64)), refs["K"]["one"][0], ("H",))["H"]
+    print("[strict2] K max|A^T b A - X^T b X| / max|X^T b X| = %.3g" % split)
+    assert split > 0.5
+    for k in rc.K_KINDS:
+        assert rc.K_ORACLE_DIST[k] / 16 <= dist[k] <= rc.K_ORACLE_DIST[k], (k, dist[k], rc.K_ORACLE_DIST[k])
 
 
 def test_criterion_rejects_stride_corruptions_at_3d_4d_inputs_and_eight_latents(refs):

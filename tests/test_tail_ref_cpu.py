@@ -50,9 +50,10 @@ def plain_tail(prm, prob, u, stats, hooks=None):
         klq = 0.5 * trace + 0.5 * m @ a - 0.5 * M + np.sum(np.log(np.abs(np.diag(u["Luu"][q])))) - np.sum(np.log(np.abs(np.diag(L_q))))
         KL += klq
         S_qi, _ = so.potri_sym(L_q)
-        if strict:
+        if strict and u["strict_two"]:          # the two-solve form: the bundle already holds dVE_dS and dVE_dmu
+            G, Kr = H, r
+        elif strict:
             import scipy.linalg
-            assert not u["strict_two"]
             Y1 = scipy.linalg.solve_triangular(u["Luu"][q], H, lower=True, trans="T")
             G = scipy.linalg.solve_triangular(u["Luu"][q], Y1.T, lower=True, trans="T")
             G = 0.5 * (G + G.T)
@@ -94,15 +95,16 @@ def plain_tail(prm, prob, u, stats, hooks=None):
 def oracle_tail(case, bundle, strict=False, hooks=None):
     from oracle import svmogp_oracle as so
     prm, prob, X, Y, rungs = case
-    p = dict(prob, strict_qf=True) if strict else prob
+    p = dict(prob, strict_qf="two_solves" if strict == "two" else True) if strict else prob
     u = so.u_algebra(prm, p, rungs)
+    assert not strict or u["strict_two"] == (strict == "two")          # True: the one-solve form; "two": the two-solve form, forced
     return plain_tail(prm, p, u, np.asarray(bundle, dtype=np.float64), hooks), u, p
 
 
 def test_plain_tail_is_the_oracles_finish(refs):
     """The restatement the corruptions are applied to gives the bits of `so.finish` (case B: ragged M, P = 2; D strict)."""
     from oracle import svmogp_oracle as so
-    for tag, variant in (("B", "default"), ("D", "strict")):
+    for tag, variant in (("B", "default"), ("D", "strict"), ("D", "strict2")):
         o = refs[tag][variant]
         got, u, p = oracle_tail(refs[tag]["case"], o["bundle"], o["strict"])
         want = so.finish(refs[tag]["case"][0], p, u, np.asarray(o["bundle"], dtype=np.float64))
@@ -164,6 +166,29 @@ def test_c_oracle_is_the_remeasured_maximum(refs):
         assert measured[k] <= c, (k, worst[k], c)
         assert c >= 1 and np.log2(c) == int(np.log2(c)) and ck[k] == max(16.0, 4.0 * c)
     assert not tr.KERNEL_EXCEPTIONS
+
+
+def test_two_solve_tail_within_c_oracle_and_rejects_the_one_solve_bundle(refs):
+    """D `strict2`: the bundle holds dVE_dS = A^T diag(beta) A and dVE_dmu = A^T alpha themselves, the tail takes G = H and
+    Kr = r.  The oracle's two-solve tail is measured against R: every kind within the present C_ORACLE except dL_dS and g_L_u, which
+    get C_ORACLE_TWO = the measured ratio rounded up to a power of two (tail_ref.py says why) and C_KERNEL_TWO = max(16, 4 C_ORACLE_TWO),
+    for this variant only.  The one-solve bundle (X^T diag(beta) X, X^T alpha) handed to the two-solve tail lands beyond C_KERNEL_TWO
+    by more than 2^10 in dL_dS and g_m_u."""
+    o, case = refs["D"]["strict2"], refs["D"]["case"]
+    assert o["strict"] == "two"
+    tr.assert_scales_dense("D strict2", o["S"])
+    got, _, _ = oracle_tail(case, o["bundle"], "two")
+    w = tr.check("oracle D strict2", got, o["R"], o["S"], tr.C_ORACLE_TWO)
+    moved = {k for k in tr.KINDS if tr.C_ORACLE_TWO[k] != tr.C_ORACLE[k]}
+    assert moved == {"dL_dS", "g_L_u"} and all(tr.C_ORACLE_TWO[k] == tr.next_pow2(w[k]) for k in moved)      # the rule, re-measured
+    assert all(tr.c_kernel_two()[k] == max(16.0, 4.0 * tr.C_ORACLE_TWO[k]) for k in tr.KINDS)
+    print("[strict2] oracle tail D strict2 %s" % " ".join("%s %.3g" % (k, w[k]) for k in tr.KINDS))
+    bad, _, _ = oracle_tail(case, refs["D"]["strict"]["bundle"], "two")
+    ck = tr.c_kernel_two()
+    for kind in ("dL_dS", "g_m_u"):
+        ratio = _worst(bad, o, kind)
+        print("[strict2] corruption one-solve bundle in the two-solve tail %-6s ratio %.3g (C_KERNEL_TWO = %g)" % (kind, ratio, ck[kind]))
+        assert ratio > 1024 * ck[kind], (kind, ratio)
 
 
 @pytest.mark.parametrize("tag", list(tc.SMALL))
